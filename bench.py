@@ -23,7 +23,13 @@ sync and the max over ranks is reported. No data-path collective in the main lin
 the ranks' ordered match lists are independent per block (the `merge` leg gathers
 them the way the frontend does, over gloo and over RCCL).
 
-Legs beside the main line: mall, limit20, shim (limit 0 and 20), concurrent, cfg3
+A plain run (`--gpus N --steps K --warmup W`) does the main line only: generate and load
+the set, warm up, time the K steps, print the line. `--dump-outputs DIR` also writes the last
+timed step's result (the arrays tsg_search returned) as DIR/<name>.npy; the inputs are
+seeded, so two builds can be compared output for output. Everything below runs under
+`--full` only.
+
+Legs beside the main line (`--full`): mall, limit20, shim (limit 0 and 20), concurrent, cfg3
 (config 3's per-GPU share: limit-20 early exit vs full scan), cfg4 (config 4 at 10 M
 entries), cfg5 (config 5: 10 M probes x 200 v2 blocks, ids sharded over the ranks),
 merge (N > 1). Every leg that searches is checked against the oracle after the timed
@@ -254,7 +260,93 @@ def parse():
                     help="auto: keep this process on the CPUs of its GPU's NUMA node (tsg_device_numa_node)")
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--keep", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the main line (mall, batched, limit20, shim, concurrent, "
+                         "cfg1/3/4/5, merge at N > 1), their oracle parity and the CPU baselines, each under "
+                         "its own option above; without it only the main line is set up, timed and reported")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the result of the last timed step (the arrays tsg_search returned) as "
+                         "DIR/<name>.npy, float32 / float64")
     return ap.parse_args()
+
+
+# options of the legs beside the main line: zero (leg off) unless --full is given
+FULL_ONLY = ("mall_steps", "cpu_baseline", "batch_queries", "limit_steps", "cfg3", "concurrent_steps", "shim_steps",
+             "merge_steps", "cfg4", "cfg1", "cfg5", "parity")
+DUMP_CAP = 64 * 2**20  # --dump-outputs: bytes over all files
+
+
+def main_line_only(args):
+    """A plain run (no --full): every leg beside the main line off, whatever its option says."""
+    if not args.full:
+        for k in FULL_ONLY:
+            setattr(args, k, 0)
+    return args
+
+
+def search_held(eng, blocks, pipe, flags):
+    """One timed step with its result kept: Engine.search_raw's tsg_search call (the same
+    prebuilt arguments) without the free. Returns (result pointer, free function); the pointer
+    is the engine's cached one, valid until the next search_raw of the same arguments."""
+    from tempo_amd import tsg
+    fn, free, cargs, rp = eng._raw_call(blocks, pipe, 0, flags)[:4]
+    rc = fn(*cargs)
+    if rc:
+        tsg._check(rc)
+    return rp, free
+
+
+def result_arrays(r, cap=DUMP_CAP):
+    """A tsg_result (tempo_amd.tsg._Result) as float arrays that hold every value exactly:
+    u8 / u32 columns and counters as they are, u64 nanosecond stamps split into whole seconds
+    and the nanoseconds within, root names as indices into the sorted distinct strings
+    (`names`: their bytes, NUL-separated). More rows than `cap` bytes hold: a fixed seeded
+    sample of them, in order (`row` = their indices in the result)."""
+    import ctypes as C
+
+    import numpy as np
+    n = int(r.n)
+    per_row = 16 * 4 + 11 * 8
+    keep = max(0, cap - 2**21) // per_row  # (2 MiB set aside for names (at most 1 MiB), metrics, file headers)
+    rows = np.arange(n) if n <= keep else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+
+    def col(ptr, width=None):
+        if not n:
+            return np.zeros((0, width) if width else (0,), np.uint64)
+        return np.ctypeslib.as_array(ptr, (n, width) if width else (n,))[rows]
+
+    out = {"row": rows.astype(np.float64), "trace_id": col(r.trace_id, 16).astype(np.float32),
+           "trace_id_len": col(r.trace_id_len).astype(np.float64)}
+    for name, ptr in (("start", r.start_ns), ("end", r.end_ns)):
+        ns = col(ptr).astype(np.uint64)
+        out[name + "_s"] = (ns // np.uint64(10**9)).astype(np.float64)
+        out[name + "_subsec_ns"] = (ns % np.uint64(10**9)).astype(np.float64)
+    for name, ptr in (("duration_ms", r.duration_ms), ("block_idx", r.block_idx), ("entry_idx", r.entry_idx)):
+        out[name] = col(ptr).astype(np.float64)
+    arena = C.string_at(r.names, r.names_len) if r.names_len else b""
+    roots = {}
+    for name, off_p, len_p in (("root_service", r.root_service_off, r.root_service_len),
+                               ("root_name", r.root_name_off, r.root_name_len)):
+        key = (col(off_p).astype(np.uint64) << np.uint64(32)) | col(len_p).astype(np.uint64)
+        uk, inv = np.unique(key, return_inverse=True)
+        roots[name] = ([arena[k >> 32:(k >> 32) + (k & 0xffffffff)] for k in uk.tolist()], inv.reshape(-1))
+    names = sorted({s for strs, _ in roots.values() for s in strs})
+    pos = {s: i for i, s in enumerate(names)}
+    for name, (strs, inv) in roots.items():
+        out[name] = np.array([pos[s] for s in strs], np.float64)[inv] if n else np.zeros(0, np.float64)
+    out["names"] = np.frombuffer(b"\0".join(names), np.uint8)[:2**18].astype(np.float32)
+    m = r.metrics  # (the counters a query determines; the timings in the struct vary run to run)
+    out["metrics"] = np.array([n, m.traces_inspected, m.blocks_inspected, m.blocks_skipped, m.bytes_inspected,
+                               m.scan_bytes], np.float64)
+    return out
+
+
+def dump_outputs(d, arrays, rank):
+    """--dump-outputs: DIR/<name>.npy per array (ranks beyond 0: <name>_rank<r>.npy)."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + ("_rank%d" % rank if rank else "") + ".npy"), a)
 
 
 def log(msg):
@@ -1103,6 +1195,7 @@ def merge_leg(args, eng, base, pipe, rank, world, dist):
 
 def main():
     args = parse()
+    main_line_only(args)
     re = rank_env(args)
     if re is None:  # --gpus N, no torchrun around us: start the ranks (nothing has touched a GPU)
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -1152,7 +1245,8 @@ def main():
     t0 = time.time()
     for th in gens.values():
         th.join()
-    log(f"rank {rank}: waited {time.time() - t0:.1f}s for the cfg3/4/5 generators")
+    if gens:
+        log(f"rank {rank}: waited {time.time() - t0:.1f}s for the cfg3/4/5 generators")
 
     streams = max(1, args.streams) if args.concurrent_steps else 1
     eng = T.Engine(devices=[local])
@@ -1204,16 +1298,26 @@ def main():
     sflags = T.SEARCH_TIME_DEFER if args.events else 0
     ev_phase = args.events // 2  # (sampled steps: i % events == events // 2, never the first step)
 
-    def timed(nsteps, rot):
+    def timed(nsteps, rot, hold=False):
+        """`hold`: the last step's result is kept (search_held) and returned as arrays."""
         step_s = []
+        held = None
         t0 = time.perf_counter()
         for i in range(nsteps):  # (tsg_search is synchronous: results are on the host when it returns)
             ts = time.perf_counter()
-            eng.search_raw(sets[i % rot], pipe, flags=sflags if args.events and i % args.events == ev_phase else 0,
-                           metrics=False)
+            fl = sflags if args.events and i % args.events == ev_phase else 0
+            if hold and i == nsteps - 1:
+                held = search_held(eng, sets[i % rot], pipe, fl)
+            else:
+                eng.search_raw(sets[i % rot], pipe, flags=fl, metrics=False)
             step_s.append(time.perf_counter() - ts)
         torch.cuda.synchronize()
-        return time.perf_counter() - t0, step_s
+        elapsed = time.perf_counter() - t0
+        if held is not None:  # (copied out and freed outside the timed region)
+            arrays = result_arrays(held[0].contents)
+            held[1](held[0])
+            return elapsed, step_s, arrays
+        return elapsed, step_s
 
     # Python's cyclic GC stays off through the timed legs (re-enabled before the CPU
     # baselines): a collection pass over this process's heap is host noise that the
@@ -1229,8 +1333,10 @@ def main():
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
-    elapsed, step_s = timed(args.steps, len(sets))
+    elapsed, step_s, *last = timed(args.steps, len(sets), hold=bool(args.dump_outputs))
     scan_ns = eng.kernel_times() if args.events else []
+    if last:
+        dump_outputs(args.dump_outputs, last[0], rank)
     if dist:
         dist.barrier()
         tt = torch.tensor([elapsed], dtype=torch.float64, device=RED_DEVICE)

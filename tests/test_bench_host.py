@@ -89,3 +89,82 @@ def test_launch_runs_ranks_with_rank_environment(tmp_path):
     assert subprocess.call(cmd, env=env, timeout=120) == 0
     got = sorted((tmp_path / f).read_text() for f in ("rank0", "rank1"))
     assert got == ["0 2 0", "1 2 1"]
+
+
+def test_plain_run_is_the_main_line_only():
+    """Without --full every leg beside the main line is off, whatever its own option says;
+    with --full the legs' options stand as given."""
+    a = bench.main_line_only(_args("--gpus", "1", "--steps", "7", "--warmup", "2", "--cfg4", "1", "--shim-steps", "9"))
+    assert all(getattr(a, k) == 0 for k in bench.FULL_ONLY)
+    assert (a.steps, a.warmup, a.sets, a.events, a.dump_outputs) == (7, 2, 4, 4, None)
+    f = bench.main_line_only(_args("--full", "--shim-steps", "9"))
+    assert (f.shim_steps, f.mall_steps, f.cfg3, f.cfg4, f.cfg5, f.parity, f.cpu_baseline) == (9, 100, None, None, 1, 1, 1)
+
+
+def _result(n, rng):
+    """A tsg_result over numpy columns (kept alive beside it)."""
+    import ctypes as C
+
+    import numpy as np
+    from tempo_amd import tsg
+    names = [b"svc-07", b"GET /carts", b"", b"svc-01"]
+    arena = b"".join(names)
+    offs = np.cumsum([0] + [len(s) for s in names[:-1]]).astype(np.uint64)
+    lens = np.array([len(s) for s in names], np.uint32)
+    pick_s, pick_n = rng.integers(0, len(names), n), rng.integers(0, len(names), n)
+    cols = dict(trace_id=rng.integers(0, 256, (n, 16), dtype=np.uint8), trace_id_len=np.full(n, 16, np.uint8),
+                start_ns=rng.integers(2**60, 2**61, n, dtype=np.uint64), end_ns=rng.integers(2**60, 2**61, n, dtype=np.uint64),
+                duration_ms=rng.integers(0, 2**32, n, dtype=np.uint32), block_idx=rng.integers(0, 10, n, dtype=np.uint32),
+                entry_idx=np.sort(rng.integers(0, 2**40, n, dtype=np.uint64)),
+                root_service_off=offs[pick_s], root_service_len=lens[pick_s],
+                root_name_off=offs[pick_n], root_name_len=lens[pick_n])
+    r = tsg._Result()
+    r.n = n
+    for k, v in cols.items():
+        cols[k] = v = np.ascontiguousarray(v)
+        setattr(r, k, v.ctypes.data_as(type(getattr(r, k))))
+    buf = C.create_string_buffer(arena, len(arena))
+    r.names, r.names_len = C.cast(buf, C.c_void_p), len(arena)
+    r.metrics.traces_inspected, r.metrics.bytes_inspected, r.metrics.scan_bytes = 12345, 2**40 + 1, 2**33 + 3
+    want = dict(cols, root_service=[names[i] for i in pick_s], root_name=[names[i] for i in pick_n])
+    return r, want, buf
+
+
+def test_result_arrays_hold_every_value_exactly(tmp_path):
+    """--dump-outputs: float arrays from which every integer of the result reads back
+    exactly (u64 nanoseconds split into seconds + the rest), names resolved."""
+    import numpy as np
+    r, want, _keep = _result(300, np.random.default_rng(3))
+    out = bench.result_arrays(r)
+    assert all(a.dtype in (np.float32, np.float64) for a in out.values())
+    u = lambda a: a.astype(np.uint64)  # noqa: E731
+    assert (out["row"] == np.arange(300)).all()
+    assert (out["trace_id"].astype(np.uint8) == want["trace_id"]).all()
+    for k in ("start", "end"):
+        assert (u(out[k + "_s"]) * np.uint64(10**9) + u(out[k + "_subsec_ns"]) == want[k + "_ns"]).all()
+    for k in ("trace_id_len", "duration_ms", "block_idx", "entry_idx"):
+        assert (u(out[k]) == want[k]).all()
+    names = bytes(out["names"].astype(np.uint8)).split(b"\0")
+    assert names == sorted(set(names))
+    for k in ("root_service", "root_name"):
+        assert [names[int(i)] for i in out[k]] == want[k]
+    assert out["metrics"].tolist() == [300, 12345, 0, 0, 2**40 + 1, 2**33 + 3]
+    bench.dump_outputs(str(tmp_path / "d"), out, 0)
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == sorted(k + ".npy" for k in out)
+    assert (np.load(tmp_path / "d" / "entry_idx.npy") == out["entry_idx"]).all()
+
+
+def test_result_arrays_sample_a_large_result_and_take_an_empty_one():
+    """More rows than the byte cap holds: the same seeded rows every time, in order, within
+    the cap; an empty result gives empty columns."""
+    import numpy as np
+    r, want, _keep = _result(5000, np.random.default_rng(4))
+    cap = 2**21 + 1000 * 152
+    a, b = bench.result_arrays(r, cap=cap), bench.result_arrays(r, cap=cap)
+    rows = a["row"].astype(np.int64)
+    assert len(rows) == 1000 and (np.diff(rows) > 0).all() and all((a[k] == b[k]).all() for k in a)
+    assert (a["entry_idx"].astype(np.uint64) == want["entry_idx"][rows]).all()
+    assert sum(x.nbytes for x in a.values()) <= cap
+    r0, _, _keep0 = _result(0, np.random.default_rng(5))
+    e = bench.result_arrays(r0)
+    assert e["trace_id"].shape == (0, 16) and len(e["root_name"]) == 0 and e["metrics"][0] == 0
