@@ -164,3 +164,192 @@ def shim_digest(per_block):
             h = ((h ^ b) * 0x100000001b3) & M
         total = (total + h) & M
     return total
+
+
+# ---- column results against the oracle ----------------------------------------------
+def oracle_columns(exp):
+    """The oracle's ordered matches as numpy columns (built once for a large result), the root
+    names as indices into `names`."""
+    import numpy as np
+    n = len(exp)
+    col = lambda f, dt: np.fromiter((m[f] for m in exp), dt, n)  # noqa: E731
+    out = {"block_idx": col("block_idx", np.uint32), "entry_idx": col("entry_idx", np.uint64),
+           "start_ns": col("start_ns", np.uint64), "end_ns": col("end_ns", np.uint64),
+           "duration_ms": col("duration_ms", np.uint32),
+           "trace_id": np.frombuffer(b"".join(m["id"] for m in exp), np.uint8).reshape(n, 16)}
+    names, index = [], {}
+    for f in ("root_service", "root_name"):
+        out[f] = np.fromiter((index.setdefault(m[f], len(index)) for m in exp), np.int64, n)
+    names = sorted(index, key=index.get)
+    out["names"] = names
+    return out
+
+
+def columns_equal_oracle(cols, gmet, ocols, omet):
+    """Engine.search_columns' result against the oracle's of the same search (oracle_columns
+    of its matches, its metrics): the four metrics, then every record in order, field by
+    field (block index, scan position, id, start, end, DurationMs, root names). Returns None
+    when equal, else a short description of the first difference."""
+    import numpy as np
+    keys = ("traces_inspected", "bytes_inspected", "blocks_inspected", "blocks_skipped")
+    got_m = (gmet.inspected_traces, gmet.inspected_bytes, gmet.inspected_blocks, gmet.skipped_blocks)
+    if got_m != tuple(omet[k] for k in keys):
+        return "metrics %r != %r" % (got_m, tuple(omet[k] for k in keys))
+    n = len(ocols["start_ns"])
+    if len(cols["start_ns"]) != n:
+        return "%d records, oracle %d" % (len(cols["start_ns"]), n)
+    if n == 0:
+        return None
+    for f in ("block_idx", "entry_idx", "start_ns", "end_ns", "duration_ms"):
+        bad = np.nonzero(cols[f] != ocols[f])[0]
+        if len(bad):
+            return "%s differs at record %d: %r != %r" % (f, bad[0], cols[f][bad[0]], ocols[f][bad[0]])
+    bad = np.nonzero((cols["trace_id"] != ocols["trace_id"]).any(axis=1))[0]
+    if len(bad):
+        return "trace_id differs at record %d" % bad[0]
+    # the engine's name indices, translated to the oracle's numbering (-1: a name it does not have)
+    oidx = {s: i for i, s in enumerate(ocols["names"])}
+    lut = np.fromiter((oidx.get(s, -1) for s in cols["names"]), np.int64, len(cols["names"]))
+    for f in ("root_service", "root_name"):
+        bad = np.nonzero(lut[cols[f]] != ocols[f])[0]
+        if len(bad):
+            return "%s differs at record %d" % (f, bad[0])
+    return None
+
+
+# ---- hand-built edge blocks (tests/test_gpu_variants.py) -----------------------------
+# The narrow kernels scan 512-entry units; lane l of a unit holds entries 4l + j and
+# 256 + 4l + j (j = 0..3). The blocks below put their matches (the "hit set" H) on those
+# edges and make every predicate decisive inside H.
+EDGE_T0 = 1_700_000_000
+EDGE_SIZES = (1, 7, 511, 512, 513, 1025, 4096, 4097)
+# the full query of the matrix: terms a..d (substring needles for b and c), whole-ms duration
+# bounds, a time range
+EDGE_TERMS = (("a", "a-hit"), ("b", "-hit"), ("c", "c-h"), ("d", "d-hit"))
+EDGE_MIN_MS, EDGE_MAX_MS = 10, 500
+EDGE_START, EDGE_END = EDGE_T0 + 1000, EDGE_T0 + 2000
+EDGE_RUN = (1000, 1700)  # the 4097 block's run of 700 consecutive hits: unit 2 whole, units 1 and 3 in part
+EDGE_VARIED_POS = 100    # (vary_dicts) the non-H entry of each block that carries the block's own values
+
+_MS, _S = 10**6, 10**9
+# role of a hit by its position in the block (every other hit passes every predicate)
+_EDGE_ROLES = {
+    # lanes 0 and 1 of step 0: one term fails alone
+    1: "fail_a", 2: "fail_b", 4: "multi_c", 5: "fail_c", 6: "fail_d",
+    # around the step boundary at 256: durations at / 1 ns under / 1 ns over the whole-ms bounds
+    251: "dur_min", 252: "dur_min_under", 253: "dur_min_over", 257: "dur_max", 258: "dur_max_under",
+    259: "dur_max_over",
+    # around the unit boundary at 512: the time range's edges, and the two span escapes
+    506: "end_eq_start", 507: "end_before_start", 509: "start_eq_end", 510: "start_after_end",
+    513: "end_zero", 514: "span_long",
+}
+
+
+def edge_hits(n):
+    """The hit set H of the edge block of n entries -> {position: role}."""
+    groups = {
+        1: [], 7: [range(0, 10)], 511: [range(0, 10), range(250, 263), range(505, 521)],
+        512: [range(0, 10), range(250, 263), range(505, 521)],
+        513: [range(0, 10), range(250, 263), range(505, 521)],
+        1025: [[511]],          # position 511 alone: the last entry of a unit
+        4096: [[255, 256]],     # 255 and 256 alone: both sides of the step boundary
+        4097: [range(0, 10), range(250, 263), range(505, 521), range(*EDGE_RUN)],
+    }[n]
+    h = {}
+    for g in groups:
+        for p in g:
+            if p < n:
+                h[p] = _EDGE_ROLES.get(p, "ok")
+    for p in range(EDGE_RUN[0], EDGE_RUN[1]):
+        if p in h:  # the run: mostly whole lanes of matches, a few single misses
+            h[p] = "fail_b" if p % 37 == 0 else "dur_max_over" if p % 41 == 0 else "ok"
+    for p in range(max(0, n - 3), n):  # the last three entries pass everything
+        h[p] = "ok"
+    return h
+
+
+def _edge_entry(tid, blk, pos, role, vary_dicts):
+    tags = {"a": ["a-hit"], "b": ["b-hit"], "c": ["c-hit"], "d": ["d-hit"], "e": ["e-hit"]}
+    start, dur = (EDGE_T0 + 1500) * _S + pos * 1000, 100 * _MS + pos
+    end = None
+    if role is None:  # outside H: term a fails; everything else varies with the position
+        h = (pos * 2654435761 + blk * 40503) >> 7
+        tags["a"] = ["a-no", "a-alt"][h % 2]
+        tags["b"] = ["b-hit", "b-no", "b-alt"][(h >> 1) % 3]
+        tags["c"] = [["c-hit"], ["c-no"], ["c-alt"], ["c-alt", "c-hit"]][(h >> 3) % 4]
+        tags["d"] = ["d-hit", "d-no", "d-alt"][(h >> 5) % 3]
+        tags["e"] = ["e-hit", "e-no", "e-alt"][(h >> 7) % 3]
+        dur = 100 * _MS if pos % 97 == 5 else (5 * _MS, 600 * _MS)[h % 2]
+        if pos % 89 != 7:
+            start = ((EDGE_T0 + 100, EDGE_T0 + 5000)[(h >> 2) % 2]) * _S + pos
+        if vary_dicts and pos == EDGE_VARIED_POS:
+            tags["a"], tags["b"] = "a-x%d" % blk, "b-x%d" % blk
+    elif role.startswith("fail_"):
+        tags[role[5:]] = ["%s-no" % role[5:]]
+    elif role == "multi_c":
+        tags["c"] = ["c-alt", "c-hit"]
+    elif role == "dur_min":
+        dur = EDGE_MIN_MS * _MS
+    elif role == "dur_min_under":
+        dur = EDGE_MIN_MS * _MS - 1
+    elif role == "dur_min_over":
+        dur = EDGE_MIN_MS * _MS + 1
+    elif role == "dur_max":
+        dur = EDGE_MAX_MS * _MS
+    elif role == "dur_max_under":
+        dur = EDGE_MAX_MS * _MS - 1
+    elif role == "dur_max_over":
+        dur = EDGE_MAX_MS * _MS + 1
+    elif role == "end_eq_start":      # end_s == req.Start
+        start = EDGE_START * _S - 100 * _MS
+    elif role == "end_before_start":  # end_s == req.Start - 1
+        start, dur = EDGE_START * _S - 100 * _MS - 1, 100 * _MS
+    elif role == "start_eq_end":      # start_s == req.End
+        start = EDGE_END * _S + _S - 1
+    elif role == "start_after_end":   # start_s == req.End + 1
+        start = (EDGE_END + 1) * _S
+    elif role == "end_zero":
+        end = 0
+    elif role == "span_long":         # a span over 65535 s
+        start, dur = (EDGE_START + 100) * _S, 70_000 * _S
+    tags["v"] = "v%03d" % (pos % 254)
+    tags["w"] = "w%03d" % (pos % 255)
+    tags["x"] = "x%03d" % (pos % 256)
+    tags["root.service.name"] = "svc-%d" % (pos % 3)
+    tags["root.name"] = "op-%d" % (pos % 5)
+    return {"id": tid, "start": start, "end": start + dur if end is None else end, "tags": tags}
+
+
+def write_edge_blocks(tmpdir, vary_dicts=False):
+    """Writes the edge blocks (snappy, 64 KiB pages) and returns their paths.
+
+    The writer takes entries in ascending id order and, as the reference's page builder does,
+    lays each page's entries out back to front, so an entry's scan position is not its rank
+    by id. An id here is [rank by id over the set, 8 bytes | scan position over the set,
+    8 bytes], both big-endian: the low half names the position, and what an entry holds is
+    decided by its position. Where the pages are cut depends (slightly) on the entries, so a
+    block is rewritten until the positions read back (the oracle's scan of it) are the ones
+    its entries were built for.
+
+    vary_dicts: one non-H entry per block carries values of `a` and `b` no other block holds,
+    so no two blocks share a dictionary of either key."""
+    paths, base = [], 0
+    for blk, n in enumerate(EDGE_SIZES):
+        hits = edge_hits(n)
+        pos_of = list(range(n))  # rank by id within the block -> scan position
+        for _ in range(6):
+            ents = [_edge_entry((base + r).to_bytes(8, "big") + (base + pos_of[r]).to_bytes(8, "big"), blk, pos_of[r],
+                                hits.get(pos_of[r]), vary_dicts) for r in range(n)]
+            path = write_block(tmpdir, "edge%d%s" % (blk, "v" if vary_dicts else ""), ents, T.ENC_SNAPPY, 64 << 10)
+            scan, _, st = O.search([O.Block(path)])
+            assert st == 0 and len(scan) == n
+            ranks = [int.from_bytes(m["id"][:8], "big") - base for m in scan]  # scan position -> rank
+            if all(pos_of[r] == s for s, r in enumerate(ranks)):
+                break
+            for s, r in enumerate(ranks):
+                pos_of[r] = s
+        else:
+            raise AssertionError("edge block %d: the page layout did not settle" % blk)
+        paths.append(path)
+        base += n
+    return paths
