@@ -62,7 +62,8 @@ extern "C" {
 #define TSG_E_NOT_FOUND 1            /* search.meta.json missing: the Go shim maps this to a no-op
                                         (backend_search_block.go:191-203) */
 #define TSG_E_CORRUPT 2              /* checksum / offset / framing error */
-#define TSG_E_UNSUPPORTED_ENCODING 3 /* search_encoding other than none/snappy, or version != v2 */
+#define TSG_E_UNSUPPORTED_ENCODING 3 /* page encoding other than none / snappy / lz4-64k / lz4-256k / lz4-1M / lz4 (and zstd for v2
+                                      * data pages), i.e. gzip or s2, or version != v2 */
 #define TSG_E_DEVICE 4               /* HIP runtime failure or no device */
 #define TSG_E_CANCELLED 5
 #define TSG_E_OOM 6
@@ -464,7 +465,9 @@ void tsg_lookup_result_free(tsg_lookup_result *r);
 /* tempodb.Find's per-block step for a batch of ids, whole on the device: the lookup above,
  * then PagedFinder.findOne (tempodb/encoding/v2/finder_paged.go:79-110) for every hit: the
  * data page its index record names (resident in HBM since tsg_v2block_open) is decompressed
- * (encodings none, snappy and zstd; others -> TSG_E_UNSUPPORTED_ENCODING for that hit) and its
+ * (encodings none, snappy, zstd and the four lz4 ones; gzip / s2 -> TSG_E_UNSUPPORTED_ENCODING
+ * for that hit; an lz4 frame with linked blocks, which the reference Writer never emits ->
+ * TSG_E_UNSUPPORTED for that hit) and its
  * objects are scanned for the exact id. One entry per lookup hit, sorted (id_idx,
  * block_idx): status TSG_OK with the object's bytes (what findOne returns), TSG_E_NOT_FOUND
  * (a bloom false positive: findOne returns nil), or the error findOne returns for that
@@ -491,7 +494,7 @@ void tsg_find_result_free(tsg_find_result *r);
  * pkg/model/trace/matches.go:33-184). meta.json dataEncoding "v1" (objects are
  * tempopb.TraceBytes) or "v2" (u32 start, u32 end seconds + TraceBytes, with the FastRange
  * and duration prefilter, pkg/model/v2/object_decoder.go:57-89). tsg_proto_block_open
- * decodes every data page (none, snappy, zstd) and every object once into per-object
+ * decodes every data page (none, snappy, zstd, lz4-64k / lz4-256k / lz4-1M / lz4) and every object once into per-object
  * columns and per-attribute-key value-set columns resident on the device; a search is one
  * kernel over the page range plus the host replay of Search's loop. */
 typedef struct tsg_proto_block tsg_proto_block;
@@ -539,7 +542,7 @@ int tsg_go_parse(int kind, const char *s, size_t n, double *f, int64_t *i);
 /* ---- block writer (tooling: synthetic data and test fixtures) ----------------- */
 /* A v2 block from caller objects (ids ascending): data pages cut at
  * index_downsample_bytes (0 = 1 MiB), index, bloom, meta.json with the given page
- * encoding (0 none, 6 snappy) and dataEncoding ("v1" / "v2"). objs: concatenated object
+ * encoding (0 none, 2..5 lz4-64k / lz4-256k / lz4-1M / lz4, 6 snappy) and dataEncoding ("v1" / "v2"). objs: concatenated object
  * bytes, obj_off: n + 1 offsets. */
 int tsg_write_v2_block(const char *block_dir, const uint8_t (*ids)[16], const uint8_t *objs,
                        const uint64_t *obj_off, size_t n, int encoding, const char *data_encoding,
@@ -551,7 +554,11 @@ int tsg_write_v2_block(const char *block_dir, const uint8_t (*ids)[16], const ui
  * entries sorted ascending by id (duplicate ids rejected), tags lowercased,
  * one flatbuffer SearchPage per v2 data page cut when the builder bytes exceed
  * page_size_bytes, index pages of 100 KiB, header, search.meta.json.
- * encoding: backend.Encoding numeric value (0 none, 6 snappy). */
+ * encoding: backend.Encoding numeric value (0 none, 2..5 the lz4 block sizes, 6 snappy). lz4 pages are
+ * the frame the reference Writer emits (independent blocks, no checksums, incompressible blocks
+ * stored); tsg_debug_set("lz4_writer_flags", bits) adds checksums for tests (1 block checksums over
+ * the decoded bytes as the reference computes them, 2 content checksum, 4 block checksums over the
+ * stored bytes as the LZ4 frame format defines them). */
 int tsg_write_search_block(const char *block_dir, const uint8_t *entries, size_t len,
                            int encoding, uint32_t page_size_bytes);
 

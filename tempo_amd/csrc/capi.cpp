@@ -2533,7 +2533,13 @@ int tsg_search_batch(tsg_ctx *ctx, const tsg_search_item *items, size_t n, uint3
     }
   return rc1;
 }
-int tsg_debug_set(const char *name, int64_t value) { return debug_set(name, value); }
+int tsg_debug_set(const char *name, int64_t value) {
+  if (name && !std::strcmp(name, "lz4_writer_flags")) {  // (the block writer's hook: common.hpp)
+    lz4_writer_flags(uint32_t(value) & 7u);
+    return TSG_OK;
+  }
+  return debug_set(name, value);
+}
 
 int tsg_kernel_times(tsg_ctx *ctx, uint64_t *ns, size_t cap, size_t *n) {
   if (!ctx || !n || (cap && !ns)) return TSG_E_INVALID;

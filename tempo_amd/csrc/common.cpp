@@ -673,3 +673,111 @@ void prof_add(const char *name, double us) {
 }
 
 }  // namespace tsg
+
+// ---- lz4 frames ---------------------------------------------------------------------------
+// The frame decoder of lz4_dev.hpp built for the host (the loaders decode lz4 pages at open;
+// findOne runs the same parser on the GPU), and the writer's encoder: a greedy hash-table
+// block compressor inside the frame the reference Writer emits (tempodb/encoding/v2/
+// pool.go:220-238; pierrec/lz4/v4 writer.go, internal/lz4stream). Any valid block decodes
+// identically; byte-identity with the Go compressor is not a goal.
+#define __device__
+#define __forceinline__ inline
+#define TSG_LZ4_HOST
+#include "lz4_dev.hpp"
+#undef __device__
+#undef __forceinline__
+
+namespace tsg {
+
+int lz4_host_decode(const uint8_t *src, size_t n, std::vector<uint8_t> &out) {
+  out.clear();
+  if (n > 0xffffffffu) return TSG_E_CORRUPT;
+  uint64_t size = 0;
+  int st = lz4dev::lz4_size(src, uint32_t(n), size);
+  if (st != TSG_OK) return st;
+  out.resize(size);
+  uint64_t len = 0;
+  st = lz4dev::lz4_decode(src, uint32_t(n), out.data(), size, len);
+  if (st != TSG_OK) out.clear();
+  return st;
+}
+
+static std::atomic<uint32_t> g_writer_flags{0};
+void lz4_writer_flags(uint32_t bits) { g_writer_flags.store(bits); }
+
+static void put_len(std::vector<uint8_t> &o, size_t v) {  // a length past its 4-bit field
+  for (; v >= 255; v -= 255) o.push_back(255);
+  o.push_back(uint8_t(v));
+}
+static void put_sequence(std::vector<uint8_t> &o, const uint8_t *lit, size_t ll, size_t off, size_t ml) {
+  const size_t mc = ml ? ml - 4 : 0;
+  o.push_back(uint8_t((ll < 15 ? ll : 15) << 4 | (mc < 15 ? mc : 15)));
+  if (ll >= 15) put_len(o, ll - 15);
+  o.insert(o.end(), lit, lit + ll);
+  if (!ml) return;  // the block's last literals
+  o.push_back(uint8_t(off));
+  o.push_back(uint8_t(off >> 8));
+  if (mc >= 15) put_len(o, mc - 15);
+}
+// One block. End-of-block rules of the format: the last 5 bytes are literals and the last
+// match starts at least 12 bytes before the end.
+static void lz4_block_encode(const uint8_t *src, size_t n, std::vector<uint8_t> &o) {
+  constexpr int kBits = 14;
+  size_t anchor = 0;
+  if (n >= 13) {
+    std::vector<uint32_t> tab(size_t(1) << kBits, 0);  // position + 1 of the last 4 bytes hashing here
+    const size_t mflimit = n - 12, matchlimit = n - 5;
+    for (size_t i = 0; i <= mflimit;) {
+      uint32_t v;
+      std::memcpy(&v, src + i, 4);
+      const uint32_t h = (v * 2654435761u) >> (32 - kBits);
+      const size_t cand = tab[h];
+      tab[h] = uint32_t(i + 1);
+      uint32_t c = 0;
+      if (cand) std::memcpy(&c, src + cand - 1, 4);
+      if (!cand || i - (cand - 1) > lz4dev::kMaxOffset || c != v) {
+        i++;
+        continue;
+      }
+      const size_t ref = cand - 1;
+      size_t ml = 4;
+      while (i + ml < matchlimit && src[ref + ml] == src[i + ml]) ml++;
+      put_sequence(o, src + anchor, i - anchor, i - ref, ml);
+      i += ml;
+      anchor = i;
+    }
+  }
+  put_sequence(o, src + anchor, n - anchor, 0, 0);
+}
+
+void lz4_frame_encode(const uint8_t *src, size_t n, int enc, std::vector<uint8_t> &out) {
+  if (!is_lz4_encoding(enc)) fail(TSG_E_INVALID, "lz4_frame_encode: not an lz4 encoding");
+  const uint32_t bits = g_writer_flags.load();
+  const bool bsum = (bits & 5) != 0, bsum_stored = (bits & 4) != 0, csum = (bits & 2) != 0;
+  const uint32_t idx = uint32_t(enc) + 2;  // lz4-64k -> 4 ... lz4 (4 MiB) -> 7
+  const size_t bmax = size_t(1) << (8 + 2 * idx);
+  out.clear();
+  put_le32(out, lz4dev::kMagic);
+  const uint8_t desc[2] = {uint8_t(0x40 | lz4dev::kFlagIndep | (bsum ? lz4dev::kFlagBlockSum : 0) |
+                                   (csum ? lz4dev::kFlagContentSum : 0)),
+                           uint8_t(idx << 4)};
+  out.push_back(desc[0]);
+  out.push_back(desc[1]);
+  out.push_back(uint8_t(lz4dev::xxh32(desc, 2) >> 8));
+  std::vector<uint8_t> comp;
+  for (size_t p = 0; p < n; p += bmax) {
+    const size_t len = std::min(bmax, n - p);
+    comp.clear();
+    lz4_block_encode(src + p, len, comp);
+    const bool stored = comp.size() >= len;
+    const uint8_t *data = stored ? src + p : comp.data();
+    const size_t dl = stored ? len : comp.size();
+    put_le32(out, uint32_t(dl) | (stored ? 0x80000000u : 0u));
+    out.insert(out.end(), data, data + dl);
+    if (bsum) put_le32(out, bsum_stored ? lz4dev::xxh32(data, dl) : lz4dev::xxh32(src + p, len));
+  }
+  put_le32(out, 0);  // end mark
+  if (csum) put_le32(out, lz4dev::xxh32(src, n));
+}
+
+}  // namespace tsg

@@ -93,6 +93,18 @@ void snappy_framed_decode(const uint8_t *src, size_t n, std::vector<uint8_t> &ou
 // compressed unless the saving is < 12.5 % (encode.go:218-235).
 void snappy_framed_encode(const uint8_t *src, size_t n, std::vector<uint8_t> &out);
 
+// ---- lz4 frames (github.com/pierrec/lz4/v4 v4.1.12 wire format) -----------
+inline bool is_lz4_encoding(int enc) { return enc >= 2 && enc <= 5; }  // lz4-64k / -256k / -1M / lz4
+// Decode the one frame of a v2 page payload (lz4_dev.hpp built for the host): TSG_OK or the error.
+int lz4_host_decode(const uint8_t *src, size_t n, std::vector<uint8_t> &out);
+// Encode like lz4.Writer with the options of tempodb/encoding/v2/pool.go:220-238: independent
+// blocks of the encoding's block size, no checksums, a block that does not shrink stored.
+void lz4_frame_encode(const uint8_t *src, size_t n, int enc, std::vector<uint8_t> &out);
+// test hook (tsg_debug_set "lz4_writer_flags"): 1 block checksums as the reference writes them
+// (over the decoded bytes), 2 content checksum, 4 block checksums as the LZ4 frame format
+// defines them (over the stored bytes; wins over 1)
+void lz4_writer_flags(uint32_t bits);
+
 // ---- strings.ToLower (ASCII exact, documented subset beyond) ---
 std::string go_to_lower(std::string_view s);
 

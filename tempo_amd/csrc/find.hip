@@ -8,6 +8,7 @@
 //   object framing / iterator      tempodb/encoding/v2/object.go:82-113, iterator.go
 //   snappy framed stream           vendor/github.com/golang/snappy/decode.go:121-232,
 //                                  block format decode_other.go:41-102
+//   lz4 frame (lz4-64k .. lz4)     vendor/github.com/pierrec/lz4/v4/reader.go, lz4_dev.hpp
 //
 // Per batch: (1) the distinct (block, record) pages of the lookup hits, (2) a size pass
 // (one lane per page walks the frame headers), (3) decode: one wave per page, each
@@ -18,8 +19,10 @@
 // one wave per page walks the objects through 64 KiB LDS windows and the lanes compare
 // each object id against the page's pending ids (first exact match, as findOne);
 // (5) the found objects are gathered into one arena for the copy back.
-// Encodings: none, snappy and zstd (zstd_dev.hpp: one lane per page); lz4 / gzip / s2
-// report TSG_E_UNSUPPORTED_ENCODING per hit (the caller's CPU path takes those blocks).
+// Encodings: none, snappy, zstd (zstd_dev.hpp: one lane per page) and the four lz4 ones
+// (lz4_dev.hpp parses the frame; find_decode_lz4_kernel: one wave per page, each block
+// decoded through a 64 KiB output ring in LDS, step (3'') below); gzip / s2 report
+// TSG_E_UNSUPPORTED_ENCODING per hit (the caller's CPU path takes those blocks).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -27,6 +30,7 @@
 #include <numeric>
 
 #include "devctx.hpp"
+#include "lz4_dev.hpp"
 #include "zstd_dev.hpp"
 
 namespace tsg {
@@ -69,6 +73,12 @@ extern "C" __global__ void __launch_bounds__(256) find_size_kernel(FindPage *pag
   if (P.enc == 7) {  // zstd: frame content sizes (or block bounds)
     uint64_t sz = 0;
     P.status = zdev::zstd_size(b, n, sz);
+    P.out_len = P.status == TSG_OK ? uint32_t(sz) : 0;
+    return;
+  }
+  if (P.enc >= 2 && P.enc <= 5) {  // lz4: the content size, or the blocks' tokens walked
+    uint64_t sz = 0;
+    P.status = lz4dev::lz4_size(b, n, sz);
     P.out_len = P.status == TSG_OK ? uint32_t(sz) : 0;
     return;
   }
@@ -155,7 +165,7 @@ extern "C" __global__ void __launch_bounds__(kFindThreads) find_decode_kernel(Fi
   __shared__ uint32_t lane_crc[kFindThreads];
   const int lane = threadIdx.x;
   FindPage &P = pages[blockIdx.x];
-  if (P.status != TSG_OK || P.enc == 7) return;  // (zstd pages: find_decode_zstd_kernel)
+  if (P.status != TSG_OK || (P.enc != 0 && P.enc != 6)) return;  // (zstd, lz4 pages: their own kernels)
   for (int i = lane; i < 256; i += kFindThreads) tab[i] = crc->table[i];
   const uint8_t *b = P.src + 6;
   const uint32_t n = P.len - 6;
@@ -292,6 +302,169 @@ extern "C" __global__ void __launch_bounds__(64) find_decode_zstd_kernel(FindPag
   const int st = zdev::zstd_decode(P.src + 6, P.len - 6, arena + P.out_off, P.out_len, len, W);
   if (st != TSG_OK) P.status = st;
   else P.out_len = uint32_t(len);  // (the size pass may hold an upper bound)
+}
+
+// (3'') lz4 pages: one wave per page, the frame's blocks one after the other. A block's
+// sequences are parsed once for the wave from compressed bytes staged in LDS in slices of
+// kLzIn; literals and matches are copied by all 64 lanes into a ring of the last 64 KiB of
+// output (the format's window: a match reaches back 65 535 bytes at most), which is written
+// to the arena every 32 KiB. A match is copied 64 bytes a step: with offset o >= 64 byte j is
+// out[d + j - o], written by an earlier step; with o < 64 the 64 bytes of a step repeat the o
+// bytes before it (byte j = out[d - o + j % o], the snappy decoder's form, re-based at every
+// step). Each step reads, meets the wave, writes and meets again, so a lane never reads a
+// byte another lane has yet to write or has already overwritten (the ring position of
+// d + j is that of d + j - 65536, which the step's own reads may still name when o > 65472).
+// Lanes hand bytes to each other through LDS only. The arena is read back only for the
+// optional xxh32 checksums (frames of the reference Writer carry none), by the workgroup that
+// stored those bytes and after a __syncthreads(): its workgroup-scope release / acquire waits
+// for the stores, and one workgroup's waves share the CU's L1, so the loads see them.
+// Linked blocks (never written by the reference): TSG_E_UNSUPPORTED for the page's hits.
+constexpr uint32_t kLzRing = 65536, kLzMask = kLzRing - 1, kLzIn = 16384, kLzChunk = 16384, kLzFlush = 32768;
+
+// xxh32 of p[0 .. n): lanes 0..3 run the four accumulators over the stripes
+__device__ uint32_t lz_wave_xxh32(const uint8_t *p, uint64_t n, int lane) {
+  uint32_t v = lane == 0 ? lz4dev::kP1 + lz4dev::kP2 : lane == 1 ? lz4dev::kP2 : lane == 2 ? 0u : 0u - lz4dev::kP1;
+  const uint64_t ns = n / 16;
+  if (lane < 4)
+    for (uint64_t i = 0; i < ns; i++) v = lz4dev::xxh_round(v, lz4dev::rd32(p + 16 * i + 4 * lane));
+  const uint32_t v0 = __shfl(v, 0, 64), v1 = __shfl(v, 1, 64), v2 = __shfl(v, 2, 64), v3 = __shfl(v, 3, 64);
+  return lz4dev::xxh_finish(n >= 16 ? lz4dev::xxh_merge(v0, v1, v2, v3) : lz4dev::kP5, p + 16 * ns, n);
+}
+
+// one compressed block src[0 .. n) -> dst[0 .. cap); every value that steers control is wave-uniform
+__device__ int32_t lz_block_wave(const uint8_t *src, uint32_t n, uint8_t *dst, uint32_t cap, uint32_t &len,
+                                 uint8_t *ring, uint8_t *ibuf, int lane) {
+  len = 0;
+  if (n == 0) return TSG_OK;
+  uint32_t ib0 = 0, ibn = 0;  // ibuf holds src[ib0 .. ib0 + ibn)
+  auto byte = [&](uint32_t t) -> uint32_t {  // t < n, never behind ib0
+    if (t >= ib0 + ibn) {
+      __syncthreads();
+      ib0 = t;
+      ibn = min(n - t, kLzIn);
+      for (uint32_t i = lane; i < ibn; i += kFindThreads) ibuf[i] = src[t + i];
+      __syncthreads();
+    }
+    return uint32_t(__builtin_amdgcn_readfirstlane(int(ibuf[t - ib0])));
+  };
+  uint32_t s = 0, d = 0, flushed = 0;
+  auto flush = [&](uint32_t upto) {  // (the ring's bytes are complete: callers have met the wave)
+    for (uint32_t i = flushed + lane; i < upto; i += kFindThreads) dst[i] = ring[i & kLzMask];
+    flushed = upto;
+    __syncthreads();
+  };
+  for (;;) {
+    if (s >= n) return TSG_E_CORRUPT;
+    const uint32_t tok = byte(s++);
+    uint32_t ll = tok >> 4;  // (n <= 4 MiB: a length stays below 2^31)
+    if (ll == 15) {
+      uint32_t x;
+      do {
+        if (s >= n) return TSG_E_CORRUPT;
+        x = byte(s++);
+        ll += x;
+      } while (x == 255);
+    }
+    if (ll > n - s || ll > cap - d) return TSG_E_CORRUPT;
+    while (ll) {
+      const uint32_t c = min(ll, kLzChunk);
+      if (s >= ib0 && s + c <= ib0 + ibn) {
+        for (uint32_t j = lane; j < c; j += kFindThreads) ring[(d + j) & kLzMask] = ibuf[s - ib0 + j];
+      } else {  // (past the staged slice: straight from the page)
+        for (uint32_t j = lane; j < c; j += kFindThreads) ring[(d + j) & kLzMask] = src[s + j];
+      }
+      s += c;
+      d += c;
+      ll -= c;
+      __syncthreads();
+      if (d - flushed >= kLzFlush) flush(d);
+    }
+    if (s == n) break;  // a block ends with literals
+    if (n - s < 2) return TSG_E_CORRUPT;
+    uint32_t off = byte(s);  // (two statements: byte() may restage the slice, in input order only)
+    off |= byte(s + 1) << 8;
+    s += 2;
+    if (off == 0 || off > d) return TSG_E_CORRUPT;
+    uint32_t ml = 4 + (tok & 15);
+    if ((tok & 15) == 15) {
+      uint32_t x;
+      do {
+        if (s >= n) return TSG_E_CORRUPT;
+        x = byte(s++);
+        ml += x;
+      } while (x == 255);
+    }
+    if (ml > cap - d) return TSG_E_CORRUPT;
+    // lane L of a step copies from `back` bytes behind its byte: o, or with o < 64 the byte
+    // L % o of the o bytes before the step
+    const uint32_t back = off >= uint32_t(kFindThreads) ? off : off + uint32_t(lane) - uint32_t(lane) % off;
+    while (ml) {
+      const uint32_t c = min(ml, kLzChunk);
+      for (uint32_t j0 = 0; j0 < c; j0 += kFindThreads) {
+        const uint32_t j = j0 + lane;
+        uint8_t v = 0;
+        if (j < c) v = ring[(d + j - back) & kLzMask];
+        __syncthreads();
+        if (j < c) ring[(d + j) & kLzMask] = v;
+        __syncthreads();
+      }
+      d += c;
+      ml -= c;
+      if (d - flushed >= kLzFlush) flush(d);
+    }
+  }
+  flush(d);
+  len = d;
+  return TSG_OK;
+}
+
+extern "C" __global__ void __launch_bounds__(kFindThreads) find_decode_lz4_kernel(FindPage *pages, uint8_t *arena) {
+  __shared__ uint8_t ring[kLzRing];
+  __shared__ uint8_t ibuf[kLzIn];
+  const int lane = threadIdx.x;
+  FindPage &P = pages[blockIdx.x];
+  if (P.status != TSG_OK || P.enc < 2 || P.enc > 5) return;
+  const uint8_t *b = P.src + 6;
+  const uint32_t n = P.len - 6;
+  uint8_t *out = arena + P.out_off;
+  lz4dev::Frame f;
+  int32_t status = lz4dev::lz4_header(b, n, f);  // (accepted by the size pass already)
+  if (status == TSG_OK && !(f.flags & lz4dev::kFlagIndep)) status = TSG_E_UNSUPPORTED;
+  lz4dev::BlockWalk w;
+  w.s = f.pos;
+  uint32_t pos = 0;
+  while (status == TSG_OK) {
+    const int r = w.next(b, n, f);
+    if (r <= 0) {
+      if (r < 0) status = TSG_E_CORRUPT;
+      break;
+    }
+    uint32_t ulen = w.size;
+    if (w.stored) {
+      if (ulen > P.out_len - pos) {
+        status = TSG_E_CORRUPT;
+        break;
+      }
+      for (uint32_t i = lane; i < ulen; i += kFindThreads) out[pos + i] = b[w.data + i];
+    } else {
+      status = lz_block_wave(b + w.data, w.size, out + pos, min(f.bmax, P.out_len - pos), ulen, ring, ibuf, lane);
+      if (status != TSG_OK) break;
+    }
+    if (f.flags & lz4dev::kFlagBlockSum) {  // over the decoded bytes (reference) or the stored ones (format)
+      __syncthreads();
+      if (lz_wave_xxh32(out + pos, ulen, lane) != w.sum && lz_wave_xxh32(b + w.data, w.size, lane) != w.sum) {
+        status = TSG_E_CORRUPT;
+        break;
+      }
+    }
+    pos += ulen;
+  }
+  if (status == TSG_OK && (f.flags & lz4dev::kFlagContentSum)) {
+    __syncthreads();
+    if (n - w.s < 4 || lz4dev::rd32(b + w.s) != lz_wave_xxh32(out, pos, lane)) status = TSG_E_CORRUPT;
+  }
+  if (status == TSG_OK && pos != P.out_len) status = TSG_E_CORRUPT;
+  if (lane == 0 && status != TSG_OK) P.status = status;
 }
 
 // (4) the page's objects against its pending ids (hit_ids[hit0 .. hit0 + nhit), 16 bytes
@@ -501,6 +674,13 @@ void device_find(DeviceCtx &dc, const std::vector<std::pair<uint32_t, V2Block *>
   for (auto &pg : pages) any_zstd = any_zstd || (pg.enc == 7 && pg.status == TSG_OK);
   if (any_zstd) {
     find_decode_zstd_kernel<<<np, 64, 0, s>>>(static_cast<FindPage *>(dpages.p), static_cast<uint8_t *>(darena.p));
+    HIP_OK(hipGetLastError());
+  }
+  bool any_lz4 = false;
+  for (auto &pg : pages) any_lz4 = any_lz4 || (pg.enc >= 2 && pg.enc <= 5 && pg.status == TSG_OK);
+  if (any_lz4) {
+    find_decode_lz4_kernel<<<np, kFindThreads, 0, s>>>(static_cast<FindPage *>(dpages.p),
+                                                       static_cast<uint8_t *>(darena.p));
     HIP_OK(hipGetLastError());
   }
   // (4) objects

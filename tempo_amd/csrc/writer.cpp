@@ -137,6 +137,7 @@ static size_t cut_data_page(std::vector<uint8_t> &file, const std::vector<uint8_
   std::vector<uint8_t> payload;
   if (enc == 6) snappy_framed_encode(objects.data(), objects.size(), payload);
   else if (enc == 0) payload = objects;
+  else if (is_lz4_encoding(enc)) lz4_frame_encode(objects.data(), objects.size(), enc, payload);
   else fail(TSG_E_UNSUPPORTED_ENCODING, std::string("writer: unsupported encoding ") + encoding_name(enc));
   uint32_t total = uint32_t(payload.size() + 6);
   put_le32(file, total);
@@ -250,7 +251,7 @@ struct SearchBlockWriter::Impl {
 };
 
 SearchBlockWriter::SearchBlockWriter(const std::string &dir, int enc, uint32_t page_size) : p_(new Impl) {
-  if (enc != 0 && enc != 6) fail(TSG_E_UNSUPPORTED_ENCODING, "writer supports none/snappy");
+  if (enc != 0 && enc != 6 && !is_lz4_encoding(enc)) fail(TSG_E_UNSUPPORTED_ENCODING, "writer supports none/snappy/lz4");
   p_->dir = dir;
   p_->enc = enc;
   p_->page_size = page_size ? page_size : 2 * 1024 * 1024;  // defaultBackendSearchBlockPageSize

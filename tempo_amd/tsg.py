@@ -36,6 +36,10 @@ TSG_E_UNSUPPORTED = 8
 TSG_E_IO = 9
 
 ENC_NONE = 0
+ENC_LZ4_64K = 2
+ENC_LZ4_256K = 3
+ENC_LZ4_1M = 4
+ENC_LZ4_4M = 5  # "lz4"
 ENC_SNAPPY = 6
 ENC_NAMES = ["none", "gzip", "lz4-64k", "lz4-256k", "lz4-1M", "lz4", "snappy", "zstd", "s2"]  # backend.Encoding.String
 
@@ -845,7 +849,8 @@ _block_closes = [0]  # BackendSearchBlock closes so far
 
 def debug_set(name: str, value: int) -> None:
     """tsg_debug_set: process-wide test hooks ("res_torn": the next `value` resident posts are
-    written torn, then repaired)."""
+    written torn, then repaired; DESIGN.md §4. "lz4_writer_flags": checksum bits of the lz4 page
+    writer, include/tsg.h)."""
     _check(lib().tsg_debug_set(name.encode(), value))
 
 
