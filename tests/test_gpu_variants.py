@@ -1,8 +1,8 @@
 """Every narrow-scan kernel instance against the oracle, on hand-built edge blocks.
 
-The narrow scan is three kernels in pool.hip (search_resident_kernel, search_static_kernel,
+The narrow scan is three kernels in pool_kernels.hpp (search_resident_kernel, search_static_kernel,
 search_pool_kernel), each a template over <NT 0..4, DUR, RANGE, NTL>: 40 instances per kernel,
-picked on the host by the query's shape (resident_symbol, pick_static, pick_pool). This file
+picked on the host by the query's shape (pool.hip with_shape: pool_fn, kernel_symbol). This file
 asks for each of the 20 (NT, DUR, RANGE) shapes on purpose and asserts, through
 tsg_metrics.path, which kind of kernel served it.
 
@@ -15,6 +15,8 @@ Instances run here (100 of the 120):
   (every unit claimed from the device counter), with and without TSG_POOL_NT=0.
 Left out: the 20 search_resident_kernel <.., NTL=false> instances. They need a lone engine
 started with TSG_POOL_NT=0, and the session's engine (default loads) is open for the whole run.
+(Their unit load, ranks and record store are the shared helpers load_unit, unit_ranks and put_rec
+that the 100 instances above run.)
 The same shapes also run on the fast kernel (TSG_NO_POOL=1) and the general path (TSG_NO_FAST=1).
 
 The fixture (tests/helpers.py write_edge_blocks): 8 blocks of 1, 7, 511, 512, 513, 1025, 4096
