@@ -62,8 +62,8 @@ extern "C" {
 #define TSG_E_NOT_FOUND 1            /* search.meta.json missing: the Go shim maps this to a no-op
                                         (backend_search_block.go:191-203) */
 #define TSG_E_CORRUPT 2              /* checksum / offset / framing error */
-#define TSG_E_UNSUPPORTED_ENCODING 3 /* page encoding other than none / snappy / lz4-64k / lz4-256k / lz4-1M / lz4 (and zstd for v2
-                                      * data pages), i.e. gzip or s2, or version != v2 */
+#define TSG_E_UNSUPPORTED_ENCODING 3 /* page encoding other than none / snappy / zstd / lz4-64k / lz4-256k / lz4-1M / lz4,
+                                      * i.e. gzip or s2, or version != v2 */
 #define TSG_E_DEVICE 4               /* HIP runtime failure or no device */
 #define TSG_E_CANCELLED 5
 #define TSG_E_OOM 6
@@ -465,7 +465,8 @@ void tsg_lookup_result_free(tsg_lookup_result *r);
 /* tempodb.Find's per-block step for a batch of ids, whole on the device: the lookup above,
  * then PagedFinder.findOne (tempodb/encoding/v2/finder_paged.go:79-110) for every hit: the
  * data page its index record names (resident in HBM since tsg_v2block_open) is decompressed
- * (encodings none, snappy, zstd and the four lz4 ones; gzip / s2 -> TSG_E_UNSUPPORTED_ENCODING
+ * (encodings none, snappy, zstd (one wave per page; a frame with a dictionary -> TSG_E_UNSUPPORTED for
+ * that hit) and the four lz4 ones; gzip / s2 -> TSG_E_UNSUPPORTED_ENCODING
  * for that hit; an lz4 frame with linked blocks, which the reference Writer never emits ->
  * TSG_E_UNSUPPORTED for that hit) and its
  * objects are scanned for the exact id. One entry per lookup hit, sorted (id_idx,
@@ -542,11 +543,21 @@ int tsg_go_parse(int kind, const char *s, size_t n, double *f, int64_t *i);
 /* ---- block writer (tooling: synthetic data and test fixtures) ----------------- */
 /* A v2 block from caller objects (ids ascending): data pages cut at
  * index_downsample_bytes (0 = 1 MiB), index, bloom, meta.json with the given page
- * encoding (0 none, 2..5 lz4-64k / lz4-256k / lz4-1M / lz4, 6 snappy) and dataEncoding ("v1" / "v2"). objs: concatenated object
+ * encoding (0 none, 2..5 lz4-64k / lz4-256k / lz4-1M / lz4, 6 snappy, 7 zstd) and dataEncoding ("v1" / "v2"). objs: concatenated object
  * bytes, obj_off: n + 1 offsets. */
 int tsg_write_v2_block(const char *block_dir, const uint8_t (*ids)[16], const uint8_t *objs,
                        const uint64_t *obj_off, size_t n, int encoding, const char *data_encoding,
                        uint32_t index_downsample_bytes);
+/* The same block from data pages the caller has encoded already (frames of another encoder in
+ * front of the device decoders): page p's payload, payloads[payload_off[p] .. payload_off[p + 1]),
+ * must decode at `encoding` to the marshalled objects ([u32 total][u32 16][id][object]) of ids
+ * page_first[p] .. page_first[p + 1] - 1 (page_first[0] = 0, the last page ends at n). The page
+ * framing, the index with its checksums, the blooms and meta.json are written here; the payloads
+ * are not checked. */
+int tsg_write_v2_block_pages(const char *block_dir, const uint8_t (*ids)[16], const uint8_t *objs,
+                             const uint64_t *obj_off, size_t n, const uint64_t *page_first,
+                             const uint8_t *payloads, const uint64_t *payload_off, size_t npages,
+                             int encoding, const char *data_encoding);
 /* Entry list wire format (little endian), one record per trace:
  *   u32 id_len, id bytes, u64 start_ns, u64 end_ns, u32 ntags,
  *   ntags x (u32 klen, key, u32 vlen, value)
@@ -554,7 +565,11 @@ int tsg_write_v2_block(const char *block_dir, const uint8_t (*ids)[16], const ui
  * entries sorted ascending by id (duplicate ids rejected), tags lowercased,
  * one flatbuffer SearchPage per v2 data page cut when the builder bytes exceed
  * page_size_bytes, index pages of 100 KiB, header, search.meta.json.
- * encoding: backend.Encoding numeric value (0 none, 2..5 the lz4 block sizes, 6 snappy). lz4 pages are
+ * encoding: backend.Encoding numeric value (0 none, 2..5 the lz4 block sizes, 6 snappy, 7 zstd). zstd pages are
+ * one RFC 8878 frame (a window over the page, the content size, blocks <= 128 KiB, Huffman literals,
+ * predefined sequence tables); tsg_debug_set("zstd_writer_flags", bits) forces other forms for tests
+ * (1 content checksum, 2 raw literals, 4 direct / 8 FSE-compressed Huffman weights, 16 FSE-described
+ * sequence tables, 32 literals-only compressed blocks). lz4 pages are
  * the frame the reference Writer emits (independent blocks, no checksums, incompressible blocks
  * stored); tsg_debug_set("lz4_writer_flags", bits) adds checksums for tests (1 block checksums over
  * the decoded bytes as the reference computes them, 2 content checksum, 4 block checksums over the

@@ -2538,6 +2538,10 @@ int tsg_debug_set(const char *name, int64_t value) {
     lz4_writer_flags(uint32_t(value) & 7u);
     return TSG_OK;
   }
+  if (name && !std::strcmp(name, "zstd_writer_flags")) {
+    zstd_writer_flags(uint32_t(value) & 63u);
+    return TSG_OK;
+  }
   return debug_set(name, value);
 }
 
@@ -2785,6 +2789,30 @@ int tsg_write_v2_block(const char *dir, const uint8_t (*ids)[16], const uint8_t 
     for (int k = 0; k < 16; k++) prm.block_id[k] = uint8_t(0x11 * (k + 1));
     prm.block_id[6] = (prm.block_id[6] & 0x0f) | 0x40;
     write_v2_block(dir, ids, o, n, prm);
+  });
+}
+
+int tsg_write_v2_block_pages(const char *dir, const uint8_t (*ids)[16], const uint8_t *objs, const uint64_t *obj_off,
+                             size_t n, const uint64_t *page_first, const uint8_t *payloads, const uint64_t *payload_off,
+                             size_t npages, int encoding, const char *data_encoding) {
+  if (!dir || !n || !npages || !ids || !objs || !obj_off || !page_first || !payloads || !payload_off) return TSG_E_INVALID;
+  return guard([&] {
+    for (size_t i = 1; i < n; i++)
+      if (bytes_compare(ids[i - 1], 16, ids[i], 16) >= 0) fail(TSG_E_INVALID, "ids must be strictly ascending");
+    if (encoding < 0 || encoding > 8) fail(TSG_E_INVALID, "unknown encoding");
+    for (size_t i = 0; i < n; i++)
+      if (obj_off[i + 1] < obj_off[i]) fail(TSG_E_INVALID, "object offsets must not decrease");
+    for (size_t p = 0; p < npages; p++)
+      if (payload_off[p + 1] < payload_off[p]) fail(TSG_E_INVALID, "payload offsets must not decrease");
+    std::vector<std::vector<uint8_t>> o(n), pl(npages);
+    for (size_t i = 0; i < n; i++) o[i].assign(objs + obj_off[i], objs + obj_off[i + 1]);
+    for (size_t p = 0; p < npages; p++) pl[p].assign(payloads + payload_off[p], payloads + payload_off[p + 1]);
+    V2Params prm;
+    prm.encoding = encoding;
+    prm.data_encoding = data_encoding ? data_encoding : "v2";
+    for (int k = 0; k < 16; k++) prm.block_id[k] = uint8_t(0x11 * (k + 1));
+    prm.block_id[6] = (prm.block_id[6] & 0x0f) | 0x40;
+    write_v2_block_pages(dir, ids, o, n, prm, page_first, pl.data(), npages);
   });
 }
 

@@ -105,6 +105,14 @@ void lz4_frame_encode(const uint8_t *src, size_t n, int enc, std::vector<uint8_t
 // defines them (over the stored bytes; wins over 1)
 void lz4_writer_flags(uint32_t bits);
 
+// ---- zstd frames (RFC 8878; zstd_enc.hpp, built in zstd_host.cpp) ------------------------------
+// One frame holding the page: a window over all of it, the content size, blocks <= 128 KiB.
+void zstd_frame_encode(const uint8_t *src, size_t n, std::vector<uint8_t> &out);
+// test hook (tsg_debug_set "zstd_writer_flags"): the zenc flag bits of zstd_enc.hpp (1 content
+// checksum, 2 raw literals, 4 direct Huffman weights, 8 FSE-compressed weights, 16 FSE-described
+// sequence tables, 32 literals-only compressed blocks)
+void zstd_writer_flags(uint32_t bits);
+
 // ---- strings.ToLower (ASCII exact, documented subset beyond) ---
 std::string go_to_lower(std::string_view s);
 

@@ -19,13 +19,15 @@
 // one wave per page walks the objects through 64 KiB LDS windows and the lanes compare
 // each object id against the page's pending ids (first exact match, as findOne);
 // (5) the found objects are gathered into one arena for the copy back.
-// Encodings: none, snappy, zstd (zstd_dev.hpp: one lane per page) and the four lz4 ones
+// Encodings: none, snappy, zstd (zstd_dev.hpp; find_decode_zstd_wave_kernel: one wave per page,
+// step (3'z) below; the older one-lane kernel behind tsg_debug_set "zstd_find_lane") and the four lz4 ones
 // (lz4_dev.hpp parses the frame; find_decode_lz4_kernel: one wave per page, each block
 // decoded through a 64 KiB output ring in LDS, step (3'') below); gzip / s2 report
 // TSG_E_UNSUPPORTED_ENCODING per hit (the caller's CPU path takes those blocks).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <numeric>
 
@@ -300,6 +302,27 @@ extern "C" __global__ void __launch_bounds__(64) find_decode_zstd_kernel(FindPag
   if (P.status != TSG_OK || P.enc != 7 || threadIdx.x != 0) return;
   uint64_t len = 0;
   const int st = zdev::zstd_decode(P.src + 6, P.len - 6, arena + P.out_off, P.out_len, len, W);
+  if (st != TSG_OK) P.status = st;
+  else P.out_len = uint32_t(len);  // (the size pass may hold an upper bound)
+}
+
+// (3'z) zstd pages, the default: one wave per page (zstd_dev.hpp, the wave decoder). Lane 0 parses
+// the headers and table descriptions and decodes the FSE sequence stream in batches of 256
+// triples into LDS; 4 lanes decode the 4 Huffman streams; all 64 lanes execute the batches, 64
+// bytes a step. A match's source is the arena itself, since a match may reach back anywhere in
+// the page: a lane loads a byte another lane stored only after the wave has waited for its
+// stores (s_waitcnt vmcnt(0)) since that byte was written, with plain loads (zstd_dev.hpp
+// keeps `settled`, the position below which every byte has reached memory, and waits only
+// before a step that reads at or above it). LDS: zdev::Work (the block's literals and the
+// tables) + zdev::WaveWork (a batch); DESIGN.md §7 has the figures.
+extern "C" __global__ void __launch_bounds__(kFindThreads) find_decode_zstd_wave_kernel(FindPage *pages, uint8_t *arena) {
+  __shared__ zdev::Work W;
+  __shared__ zdev::WaveWork X;
+  FindPage &P = pages[blockIdx.x];
+  if (P.status != TSG_OK || P.enc != 7) return;
+  uint64_t len = 0;
+  const int st = zdev::zstd_decode_wave(P.src + 6, P.len - 6, arena + P.out_off, P.out_len, len, W, X, threadIdx.x);
+  if (threadIdx.x != 0) return;
   if (st != TSG_OK) P.status = st;
   else P.out_len = uint32_t(len);  // (the size pass may hold an upper bound)
 }
@@ -582,6 +605,9 @@ extern "C" __global__ void __launch_bounds__(256) find_gather_kernel(const FindH
 }
 
 // ---- host -------------------------------------------------------------------------------
+static std::atomic<bool> g_zstd_lane{false};  // test hook (tsg_debug_set "zstd_find_lane"): the one-lane zstd decoder
+void find_zstd_lane(bool on) { g_zstd_lane.store(on); }
+
 static void crc_tables(CrcArgs &c) {
   for (uint32_t i = 0; i < 256; i++) {
     uint32_t r = i;
@@ -673,7 +699,11 @@ void device_find(DeviceCtx &dc, const std::vector<std::pair<uint32_t, V2Block *>
   bool any_zstd = false;
   for (auto &pg : pages) any_zstd = any_zstd || (pg.enc == 7 && pg.status == TSG_OK);
   if (any_zstd) {
-    find_decode_zstd_kernel<<<np, 64, 0, s>>>(static_cast<FindPage *>(dpages.p), static_cast<uint8_t *>(darena.p));
+    if (g_zstd_lane.load(std::memory_order_relaxed))
+      find_decode_zstd_kernel<<<np, 64, 0, s>>>(static_cast<FindPage *>(dpages.p), static_cast<uint8_t *>(darena.p));
+    else
+      find_decode_zstd_wave_kernel<<<np, kFindThreads, 0, s>>>(static_cast<FindPage *>(dpages.p),
+                                                               static_cast<uint8_t *>(darena.p));
     HIP_OK(hipGetLastError());
   }
   bool any_lz4 = false;

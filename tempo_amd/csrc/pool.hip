@@ -407,6 +407,10 @@ int debug_set(const char *name, int64_t value) {
     g_xsplit.store(value != 0);
     return TSG_OK;
   }
+  if (!std::strcmp(name, "zstd_find_lane")) {  // (find.hip: 1 = the one-lane zstd page decoder)
+    find_zstd_lane(value != 0);
+    return TSG_OK;
+  }
   if (!std::strcmp(name, "lb_bitmap")) {
     g_lb_bitmap.store(uint32_t(std::min<int64_t>(2, std::max<int64_t>(0, value))));
     return TSG_OK;

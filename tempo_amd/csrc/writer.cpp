@@ -132,18 +132,22 @@ static void marshal_object(std::vector<uint8_t> &o, const uint8_t *id, size_t id
   o.insert(o.end(), id, id + idl);
   o.insert(o.end(), obj, obj + n);
 }
+static size_t put_data_page(std::vector<uint8_t> &file, const uint8_t *payload, size_t n) {
+  uint32_t total = uint32_t(n + 6);
+  put_le32(file, total);
+  put_le16(file, 0);
+  file.insert(file.end(), payload, payload + n);
+  return total;
+}
 // CutPage: compress the object buffer, page = [u32 total][u16 0][payload] (page.go:110-146)
 static size_t cut_data_page(std::vector<uint8_t> &file, const std::vector<uint8_t> &objects, int enc) {
   std::vector<uint8_t> payload;
   if (enc == 6) snappy_framed_encode(objects.data(), objects.size(), payload);
   else if (enc == 0) payload = objects;
   else if (is_lz4_encoding(enc)) lz4_frame_encode(objects.data(), objects.size(), enc, payload);
+  else if (enc == 7) zstd_frame_encode(objects.data(), objects.size(), payload);
   else fail(TSG_E_UNSUPPORTED_ENCODING, std::string("writer: unsupported encoding ") + encoding_name(enc));
-  uint32_t total = uint32_t(payload.size() + 6);
-  put_le32(file, total);
-  put_le16(file, 0);
-  file.insert(file.end(), payload.begin(), payload.end());
-  return total;
+  return put_data_page(file, payload.data(), payload.size());
 }
 
 // StreamingSearchBlock.Append per entry (streaming_search_block.go:80-95): one
@@ -251,7 +255,8 @@ struct SearchBlockWriter::Impl {
 };
 
 SearchBlockWriter::SearchBlockWriter(const std::string &dir, int enc, uint32_t page_size) : p_(new Impl) {
-  if (enc != 0 && enc != 6 && !is_lz4_encoding(enc)) fail(TSG_E_UNSUPPORTED_ENCODING, "writer supports none/snappy/lz4");
+  if (enc != 0 && enc != 6 && enc != 7 && !is_lz4_encoding(enc))
+    fail(TSG_E_UNSUPPORTED_ENCODING, "writer supports none/snappy/lz4/zstd");
   p_->dir = dir;
   p_->enc = enc;
   p_->page_size = page_size ? page_size : 2 * 1024 * 1024;  // defaultBackendSearchBlockPageSize
@@ -381,6 +386,22 @@ static std::string b64(const uint8_t *p, size_t n) {
 
 void write_v2_block(const std::string &dir, const uint8_t (*ids)[16], const std::vector<std::vector<uint8_t>> &objs,
                     uint64_t n, const V2Params &prm) {
+  write_v2_block_pages(dir, ids, objs, n, prm, nullptr, nullptr, 0);
+}
+
+// The same block from pages the caller has encoded already: page p's payload (prm.encoding)
+// holds the marshalled objects of ids [page_first[p], page_first[p + 1]); its index record
+// carries the last of those ids, as the buffered appender's would.
+void write_v2_block_pages(const std::string &dir, const uint8_t (*ids)[16], const std::vector<std::vector<uint8_t>> &objs,
+                          uint64_t n, const V2Params &prm, const uint64_t *page_first,
+                          const std::vector<uint8_t> *payloads, size_t npages) {
+  if (payloads) {
+    if (!npages || page_first[0] != 0) fail(TSG_E_INVALID, "pages must start at the first id");
+    for (size_t p = 1; p < npages; p++)
+      if (page_first[p] <= page_first[p - 1]) fail(TSG_E_INVALID, "every page holds at least one id");
+    if (page_first[npages - 1] >= n) fail(TSG_E_INVALID, "page beyond the ids");
+  }
+  size_t next_page = 0;
   // bloom
   uint64_t m, k;
   bloom_estimate(n ? n : 1, prm.bloom_fp, m, k);
@@ -409,8 +430,12 @@ void write_v2_block(const std::string &dir, const uint8_t (*ids)[16], const std:
     }
     cb += written;
     cur.id.assign(id, id + 16);
-    if (cb > long(prm.index_downsample_bytes)) {
-      size_t f = cut_data_page(file, objbuf, prm.encoding);
+    const bool cut = payloads ? (i + 1 == n || (next_page + 1 < npages && i + 1 == page_first[next_page + 1]))
+                              : cb > long(prm.index_downsample_bytes);
+    if (cut) {
+      size_t f = payloads ? put_data_page(file, payloads[next_page].data(), payloads[next_page].size())
+                          : cut_data_page(file, objbuf, prm.encoding);
+      next_page++;
       objbuf.clear();
       off += f;
       cur.length += uint32_t(f);

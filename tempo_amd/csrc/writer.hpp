@@ -62,6 +62,10 @@ void bloom_estimate(uint64_t n, double fp, uint64_t &m, uint64_t &k);
 uint32_t bloom_shard_count(double fp, uint64_t shard_size, uint64_t n);
 void write_v2_block(const std::string &dir, const uint8_t (*ids)[16], const std::vector<std::vector<uint8_t>> &objs,
                     uint64_t n, const V2Params &prm);
+// pages already encoded by the caller (payloads == nullptr: write_v2_block)
+void write_v2_block_pages(const std::string &dir, const uint8_t (*ids)[16], const std::vector<std::vector<uint8_t>> &objs,
+                          uint64_t n, const V2Params &prm, const uint64_t *page_first,
+                          const std::vector<uint8_t> *payloads, size_t npages);
 
 // synth.cpp
 void synth_search_block(const std::string &dir, uint64_t n, uint64_t seed, int profile, int enc, uint32_t page_size);

@@ -5,6 +5,9 @@
 //
 // One lane decodes one page (sequential by nature: bit-serial FSE / Huffman states);
 // its tables and the block's literals live in the workgroup's LDS, the output in HBM.
+// The wave decoder at the end of this file is the device default (all 64 lanes copy; lane 0
+// keeps the bit-serial parts); the one-lane decoder stays for the host loaders and as the
+// comparison (tsg_debug_set "zstd_find_lane").
 // Supported: any number of frames per page (skippable frames skipped), raw / RLE /
 // compressed blocks, raw / RLE / Huffman (1 or 4 streams, FSE or direct weights, treeless
 // reuse) literals, predefined / RLE / FSE / repeat sequence tables, repeat offsets, the
@@ -15,6 +18,10 @@
 #include <hip/hip_runtime.h>
 #endif
 #include <cstdint>
+
+#ifndef ZDEV_STAT  // (tools/zstd_host_check.cpp counts the forms a frame uses)
+#define ZDEV_STAT(...)
+#endif
 
 namespace tsg {
 namespace zdev {
@@ -51,7 +58,7 @@ struct BitsBack {
   const uint64_t *w;  // 8-byte aligned base
   int64_t start;      // absolute bit index of the stream's first bit
   int64_t pos;        // absolute bit index just above the next bit to read
-  __device__ uint32_t read(int n) {
+  __device__ __forceinline__ uint32_t read(int n) {
     if (n == 0) return 0;
     pos -= n;
     int64_t lo = pos;
@@ -69,7 +76,7 @@ struct BitsBack {
     v &= (1ull << k) - 1;
     return uint32_t(v << under);
   }
-  __device__ int64_t left() const { return pos - start; }  // bits not consumed (< 0: overflowed)
+  __device__ __forceinline__ int64_t left() const { return pos - start; }  // bits not consumed (< 0: overflowed)
 };
 // a backward stream over [p, p + n): the marker bit (highest set bit of the last byte) is not data
 __device__ __forceinline__ bool bits_back_init(BitsBack &b, const uint8_t *p, uint32_t n) {
@@ -87,7 +94,7 @@ struct BitsFwd {
   const uint8_t *p;
   uint32_t n;    // bytes available
   uint64_t bit;  // bits consumed
-  __device__ bool read(int k, uint32_t &v) {
+  __device__ __forceinline__ bool read(int k, uint32_t &v) {
     if (bit + uint64_t(k) > uint64_t(n) * 8) return false;
     v = 0;
     for (int i = 0; i < k; i++) {
@@ -97,7 +104,7 @@ struct BitsFwd {
     bit += uint64_t(k);
     return true;
   }
-  __device__ uint32_t bytes_used() const { return uint32_t((bit + 7) >> 3); }
+  __device__ __forceinline__ uint32_t bytes_used() const { return uint32_t((bit + 7) >> 3); }
 };
 
 // ---- FSE ---------------------------------------------------------------------------------
@@ -108,7 +115,7 @@ struct Fse {  // decoding table (in LDS)
   int al;  // accuracy log
 };
 // table from normalized counts (RFC 8878 4.1.1: symbol spreading, then states)
-__device__ bool fse_build(Fse &t, const int16_t *norm, int nsym, int al, uint16_t *scratch) {
+__device__ __forceinline__ bool fse_build(Fse &t, const int16_t *norm, int nsym, int al, uint16_t *scratch) {
   const uint32_t size = 1u << al;
   if (al > 9 || nsym > 256) return false;
   uint32_t high = size;
@@ -139,7 +146,7 @@ __device__ bool fse_build(Fse &t, const int16_t *norm, int nsym, int al, uint16_
   return true;
 }
 // FSE_Table_Description (RFC 8878 4.1.1) from a forward stream, then the table
-__device__ bool fse_read(Fse &t, BitsFwd &in, int max_al, int max_sym, int16_t *norm, uint16_t *scratch) {
+__device__ __forceinline__ bool fse_read(Fse &t, BitsFwd &in, int max_al, int max_sym, int16_t *norm, uint16_t *scratch) {
   uint32_t v;
   if (!in.read(4, v)) return false;
   const int al = 5 + int(v);
@@ -192,7 +199,7 @@ struct Huf {
   uint8_t nb[2048];
   int maxb;  // 0: no table yet
 };
-__device__ bool huf_from_weights(Huf &h, const uint8_t *w, int n) {
+__device__ __forceinline__ bool huf_from_weights(Huf &h, const uint8_t *w, int n) {
   // weights of the n transmitted symbols; the last symbol's weight is implied
   uint32_t sum = 0;
   for (int i = 0; i < n; i++) {
@@ -230,11 +237,12 @@ __device__ bool huf_from_weights(Huf &h, const uint8_t *w, int n) {
   return true;
 }
 // Huffman_Tree_Description (RFC 8878 4.2.1): returns the bytes it took, 0 on error
-__device__ uint32_t huf_read(Huf &h, const uint8_t *p, uint32_t n, Fse &wt, int16_t *norm, uint16_t *scratch,
+__device__ __forceinline__ uint32_t huf_read(Huf &h, const uint8_t *p, uint32_t n, Fse &wt, int16_t *norm, uint16_t *scratch,
                              uint8_t *wbuf) {
   if (n < 1) return 0;
   const uint32_t hb = p[0];
   int nw = 0;
+  ZDEV_STAT(g_zstat.weights[hb >= 128]++;)
   if (hb >= 128) {  // direct 4-bit weights
     nw = int(hb) - 127;
     const uint32_t bytes = uint32_t(nw + 1) / 2;
@@ -275,7 +283,7 @@ __device__ uint32_t huf_read(Huf &h, const uint8_t *p, uint32_t n, Fse &wt, int1
   return 1 + cs;
 }
 // one Huffman stream: exactly `count` symbols, every bit consumed
-__device__ bool huf_stream(const Huf &h, const uint8_t *p, uint32_t n, uint8_t *out, uint32_t count) {
+__device__ __forceinline__ bool huf_stream(const Huf &h, const uint8_t *p, uint32_t n, uint8_t *out, uint32_t count) {
   BitsBack b;
   if (!bits_back_init(b, p, n)) return false;
   const uint32_t mask = (1u << h.maxb) - 1;
@@ -295,7 +303,7 @@ __device__ __forceinline__ uint64_t ld64(const uint8_t *p) {
   return v;
 }
 __device__ __forceinline__ uint64_t rotl64(uint64_t x, int r) { return (x << r) | (x >> (64 - r)); }
-__device__ uint64_t xxh64(const uint8_t *p, uint64_t n) {
+__device__ __forceinline__ uint64_t xxh64(const uint8_t *p, uint64_t n) {
   const uint64_t P1 = 11400714785074694791ull, P2 = 14029467366897019727ull, P3 = 1609587929392839161ull,
                  P4 = 9650029242287828579ull, P5 = 2870177450012600261ull;
   uint64_t h, i = 0;
@@ -350,7 +358,7 @@ struct Work {  // one page's decoder state (LDS)
 
 // frame header: returns header bytes (0 on error); content size (or ~0 when absent),
 // single segment, checksum flag
-__device__ uint32_t frame_header(const uint8_t *p, uint32_t n, uint64_t &fcs, bool &csum, int &status) {
+__device__ __forceinline__ uint32_t frame_header(const uint8_t *p, uint32_t n, uint64_t &fcs, bool &csum, int &status) {
   if (n < 5) return 0;
   const uint32_t fhd = p[4];
   const uint32_t fcs_flag = fhd >> 6, single = (fhd >> 5) & 1, did_flag = fhd & 3;
@@ -378,7 +386,7 @@ __device__ uint32_t frame_header(const uint8_t *p, uint32_t n, uint64_t &fcs, bo
 }
 
 // Upper bound (or exact size) of the decoded bytes of a zstd payload; 0 status = ok
-__device__ int zstd_size(const uint8_t *p, uint32_t n, uint64_t &out) {
+__device__ __forceinline__ int zstd_size(const uint8_t *p, uint32_t n, uint64_t &out) {
   out = 0;
   uint32_t s = 0;
   while (s < n) {
@@ -422,9 +430,10 @@ __device__ int zstd_size(const uint8_t *p, uint32_t n, uint64_t &out) {
 }
 
 // Sequences: decode and execute (RFC 8878 3.1.1.3.2, 3.1.1.4)
-__device__ int seq_table(Fse &t, int mode, const uint8_t *p, uint32_t n, uint32_t &used, const int16_t *def,
+__device__ __forceinline__ int seq_table(Fse &t, int mode, const uint8_t *p, uint32_t n, uint32_t &used, const int16_t *def,
                          int defn, int defal, int max_al, int max_sym, Work &W, bool &have) {
   used = 0;
+  ZDEV_STAT(g_zstat.seq_mode[mode]++;)
   if (mode == 0) {  // predefined
     for (int i = 0; i < defn; i++) W.norm[i] = def[i];
     if (!fse_build(t, W.norm, defn, defal, W.scratch)) return TSG_E_CORRUPT;
@@ -449,7 +458,7 @@ struct FrameState {
   bool have_ll, have_of, have_ml;
 };
 
-__device__ int block_compressed(const uint8_t *p, uint32_t n, uint8_t *out, uint64_t &pos, uint64_t cap,
+__device__ __forceinline__ int block_compressed(const uint8_t *p, uint32_t n, uint8_t *out, uint64_t &pos, uint64_t cap,
                                 uint64_t frame_start, Work &W, FrameState &F) {
   // ---- literals section
   if (n < 1) return TSG_E_CORRUPT;
@@ -599,7 +608,7 @@ __device__ int block_compressed(const uint8_t *p, uint32_t n, uint8_t *out, uint
 }
 
 // the whole payload (DecodeAll): frames back to back into out[0..cap); *len = bytes written
-__device__ int zstd_decode(const uint8_t *p, uint32_t n, uint8_t *out, uint64_t cap, uint64_t &len, Work &W) {
+__device__ __forceinline__ int zstd_decode(const uint8_t *p, uint32_t n, uint8_t *out, uint64_t cap, uint64_t &len, Work &W) {
   uint64_t pos = 0;
   uint32_t s = 0;
   W.huf.maxb = 0;
@@ -650,6 +659,337 @@ __device__ int zstd_decode(const uint8_t *p, uint32_t n, uint8_t *out, uint64_t 
       if (n - s < 4) return TSG_E_CORRUPT;
       const uint32_t want = uint32_t(p[s]) | uint32_t(p[s + 1]) << 8 | uint32_t(p[s + 2]) << 16 | uint32_t(p[s + 3]) << 24;
       if (uint32_t(xxh64(out + fstart, pos - fstart)) != want) return TSG_E_CORRUPT;
+      s += 4;
+    }
+  }
+  len = pos;
+  return TSG_OK;
+}
+
+// ---- the wave decoder --------------------------------------------------------------------------
+// The same frames decoded by a whole wave (find.hip: find_decode_zstd_wave_kernel, one wave per
+// page). What is serial by nature stays on one lane: the headers and table descriptions
+// (3.1.1.3.1.1, 4.2.1, 4.1.1) and the FSE sequence bitstream (3.1.1.3.2.1), which lane 0 decodes in
+// batches of kSeqBatch {literal length, match length, offset} triples (repeat offsets resolved,
+// 3.1.1.5) into LDS. The 4 Huffman streams of a literals section (4.2.2) are decoded by 4 lanes
+// at once, and every copy (raw / RLE blocks, raw / RLE literals, the literals and the match of
+// each sequence, 3.1.1.4) is done by all lanes, kLanes bytes a step: with offset o >= kLanes byte
+// j of a step is out[d + j - o], with o < kLanes the step's bytes repeat the o bytes before it,
+// byte j = out[d - o + j % o]. Either way a step reads only bytes below its own first byte d.
+// A match may reach back anywhere in the frame, so its source is the output itself (the arena
+// in HBM), not a ring in LDS. The hand-off rule: a lane may load a byte another lane stored only
+// after that store has completed, so before a step whose highest source byte is not below
+// `settled` the wave waits for all its outstanding stores (s_waitcnt vmcnt(0)) and `settled`
+// moves up to the step's d; the loads are plain loads (no nt), served by the CU's L1 / L2 which
+// the completed stores have reached. Steps that reach further back issue without waiting.
+// Every value that steers control is wave-uniform (lane 0's results cross through WaveWork::u
+// and a barrier); every length, offset and table index is checked before use, by the code below
+// whether it runs on the device or, with kLanes = 1, in the host build (tools/zstd_host_check.cpp).
+#ifdef TSG_ZSTD_HOST
+constexpr uint32_t kLanes = 1;
+inline void wave_sync() {}
+inline void wave_stores_done() {}
+inline uint32_t wave_uniform(uint32_t v) { return v; }
+#else
+constexpr uint32_t kLanes = 64;
+__device__ __forceinline__ void wave_sync() { __syncthreads(); }
+__device__ __forceinline__ void wave_stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+__device__ __forceinline__ uint32_t wave_uniform(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
+#endif
+constexpr uint32_t kSeqBatch = 256;
+struct SeqRec {
+  uint32_t ll, ml, off;
+};
+struct WaveWork {  // LDS beside Work
+  SeqRec seq[kSeqBatch];
+  uint32_t u[20];  // what lane 0 hands to the wave
+  uint32_t ok[4];  // the 4 Huffman streams' results
+};
+
+// Literals_Section_Header (3.1.1.3.1.1); false: corrupt
+struct LitHdr {
+  uint32_t type, regen, csize, hdr, nstreams;
+};
+__device__ __forceinline__ bool literals_header(const uint8_t *p, uint32_t n, LitHdr &h) {
+  if (n < 1) return false;
+  const uint32_t b0 = p[0], sf = (b0 >> 2) & 3;
+  h.type = b0 & 3;
+  h.csize = 0;
+  h.nstreams = 1;
+  if (h.type <= 1) {
+    h.hdr = sf == 0 || sf == 2 ? 1 : sf == 1 ? 2 : 3;
+    if (n < h.hdr) return false;
+    h.regen = h.hdr == 1 ? b0 >> 3 : (b0 >> 4) + (uint32_t(p[1]) << 4) + (h.hdr == 3 ? uint32_t(p[2]) << 12 : 0u);
+  } else {
+    h.hdr = sf <= 1 ? 3 : sf + 2;
+    if (n < h.hdr) return false;
+    uint64_t v = 0;
+    for (uint32_t i = 0; i < h.hdr; i++) v |= uint64_t(p[i]) << (8 * i);
+    const int bits = sf <= 1 ? 10 : (sf == 2 ? 14 : 18);
+    h.regen = uint32_t((v >> 4) & ((1ull << bits) - 1));
+    h.csize = uint32_t((v >> (4 + bits)) & ((1ull << bits) - 1));
+    h.nstreams = sf == 0 ? 1 : 4;
+  }
+  ZDEV_STAT(g_zstat.lit[h.type]++; if (h.type >= 2) g_zstat.streams[h.nstreams == 4]++;)
+  if (h.regen > kMaxBlock) return false;
+  const uint32_t body = h.type == 0 ? h.regen : h.type == 1 ? 1u : h.csize;
+  return body <= n - h.hdr;
+}
+
+struct WaveState {  // per frame; the fields after `settled` are lane 0's alone
+  uint64_t settled;  // every output byte below this has reached memory
+  FrameState F;
+};
+
+// one sequence executed by the wave (3.1.1.4): literals, then the match; wave-uniform arguments
+__device__ __forceinline__ int wave_sequence(uint8_t *out, uint64_t &pos, uint64_t cap, uint64_t frame_start, const uint8_t *lit,
+                                    uint32_t &lit_pos, uint32_t regen, uint32_t ll, uint32_t ml, uint32_t off,
+                                    uint64_t &settled, uint32_t lane) {
+  if (ll > regen - lit_pos || uint64_t(ll) + ml > cap - pos) return TSG_E_CORRUPT;
+  for (uint32_t j = lane; j < ll; j += kLanes) out[pos + j] = lit[lit_pos + j];
+  lit_pos += ll;
+  pos += ll;
+  if (off == 0 || off > pos - frame_start) return TSG_E_CORRUPT;
+  const uint32_t back = off >= kLanes ? off : off + lane - lane % off;
+  for (uint32_t j0 = 0; j0 < ml; j0 += kLanes) {
+    const uint64_t d = pos + j0;
+    const uint32_t c = ml - j0 < kLanes ? ml - j0 : kLanes;
+    const uint64_t src_hi = off >= kLanes ? d + c - 1 - off : d - 1;  // the step's highest source byte
+    if (src_hi >= settled) {
+      wave_stores_done();
+      settled = d;
+    }
+    if (lane < c) out[d + lane] = out[d + lane - back];
+  }
+  pos += ml;
+  return TSG_OK;
+}
+
+__device__ __forceinline__ int block_compressed_wave(const uint8_t *p, uint32_t n, uint8_t *out, uint64_t &pos, uint64_t cap,
+                                            uint64_t frame_start, Work &W, WaveWork &X, WaveState &S, uint32_t lane) {
+  // ---- literals section: lane 0 reads the header and the tree, then the lanes fill W.lit
+  if (lane == 0) {
+    LitHdr h{0, 0, 0, 0, 1};
+    uint32_t st = TSG_OK, t = 0;
+    if (!literals_header(p, n, h)) st = TSG_E_CORRUPT;
+    uint32_t so[4] = {0, 0, 0, 0}, sl[4] = {0, 0, 0, 0}, sc[4] = {0, 0, 0, 0};
+    if (st == TSG_OK && h.type >= 2) {
+      if (h.type == 2) {
+        t = huf_read(W.huf, p + h.hdr, h.csize, W.wt, W.norm, W.scratch, W.wbuf);
+        if (!t) st = TSG_E_CORRUPT;
+      } else if (!W.huf.maxb) {
+        st = TSG_E_CORRUPT;  // treeless without a previous table
+      }
+      if (st == TSG_OK) {
+        const uint32_t o = h.hdr + t, len = h.csize - t;  // (t <= csize: huf_read stays inside it)
+        if (h.nstreams == 1) {
+          so[0] = o;
+          sl[0] = len;
+          sc[0] = h.regen;
+        } else if (len < 6) {
+          st = TSG_E_CORRUPT;
+        } else {  // Jump_Table (4.2.2)
+          const uint32_t l1 = uint32_t(p[o]) | uint32_t(p[o + 1]) << 8, l2 = uint32_t(p[o + 2]) | uint32_t(p[o + 3]) << 8,
+                         l3 = uint32_t(p[o + 4]) | uint32_t(p[o + 5]) << 8, seg = (h.regen + 3) / 4;
+          if (uint64_t(l1) + l2 + l3 > len - 6 || h.regen < 3 * seg) {
+            st = TSG_E_CORRUPT;
+          } else {
+            so[0] = o + 6, so[1] = so[0] + l1, so[2] = so[1] + l2, so[3] = so[2] + l3;
+            sl[0] = l1, sl[1] = l2, sl[2] = l3, sl[3] = len - 6 - l1 - l2 - l3;
+            sc[0] = sc[1] = sc[2] = seg, sc[3] = h.regen - 3 * seg;
+          }
+        }
+      }
+    }
+    X.u[0] = st, X.u[1] = h.type, X.u[2] = h.regen, X.u[3] = h.hdr, X.u[4] = h.nstreams;
+    X.u[5] = h.hdr + (h.type == 0 ? h.regen : h.type == 1 ? 1u : h.csize);  // where the sequences section starts
+    for (int q = 0; q < 4; q++) X.u[6 + q] = so[q], X.u[10 + q] = sl[q], X.u[14 + q] = sc[q];
+  }
+  wave_sync();
+  if (X.u[0] != TSG_OK) return int(X.u[0]);
+  const uint32_t ltype = X.u[1], regen = X.u[2], lhdr = X.u[3], nstreams = X.u[4];
+  uint32_t o = X.u[5];
+  if (ltype == 0) {
+    for (uint32_t i = lane; i < regen; i += kLanes) W.lit[i] = p[lhdr + i];
+  } else if (ltype == 1) {
+    const uint8_t v = p[lhdr];
+    for (uint32_t i = lane; i < regen; i += kLanes) W.lit[i] = v;
+  } else {
+    uint32_t at = 0;  // stream q regenerates W.lit[at ..)
+    for (uint32_t q = 0; q < nstreams; q++) {
+      if (q % kLanes == lane) X.ok[q] = huf_stream(W.huf, p + X.u[6 + q], X.u[10 + q], W.lit + at, X.u[14 + q]) ? 1u : 0u;
+      at += X.u[14 + q];
+    }
+  }
+  wave_sync();
+  if (ltype >= 2)
+    for (uint32_t q = 0; q < nstreams; q++)
+      if (!X.ok[q]) return TSG_E_CORRUPT;
+  // ---- sequences section: header and tables on lane 0
+  BitsBack b{nullptr, 0, 0};
+  uint32_t sll = 0, sof = 0, sml = 0;
+  if (lane == 0) {
+    uint32_t st = TSG_OK, nseq = 0;
+    if (o >= n) {
+      st = TSG_E_CORRUPT;
+    } else {
+      nseq = p[o];
+      if (nseq < 128) {
+        o += 1;
+      } else if (nseq < 255) {
+        if (n - o < 2) st = TSG_E_CORRUPT;
+        else nseq = ((nseq - 128) << 8) + p[o + 1], o += 2;
+      } else {
+        if (n - o < 3) st = TSG_E_CORRUPT;
+        else nseq = uint32_t(p[o + 1]) + (uint32_t(p[o + 2]) << 8) + 0x7F00, o += 3;
+      }
+    }
+    if (st == TSG_OK && nseq) {
+      if (n - o < 1) {
+        st = TSG_E_CORRUPT;
+      } else {
+        const uint32_t modes = p[o++];
+        uint32_t used = 0;
+        if (modes & 3) st = TSG_E_CORRUPT;
+        if (st == TSG_OK) st = uint32_t(seq_table(W.ll, int(modes >> 6), p + o, n - o, used, kLLDef, 36, 6, 9, kLLMax, W, S.F.have_ll));
+        o += used, used = 0;
+        if (st == TSG_OK) st = uint32_t(seq_table(W.of, int((modes >> 4) & 3), p + o, n - o, used, kOFDef, 29, 5, 8, kOFMax, W, S.F.have_of));
+        o += used, used = 0;
+        if (st == TSG_OK) st = uint32_t(seq_table(W.ml, int((modes >> 2) & 3), p + o, n - o, used, kMLDef, 53, 6, 9, kMLMax, W, S.F.have_ml));
+        o += used;
+        if (st == TSG_OK && (o >= n || !bits_back_init(b, p + o, n - o))) st = TSG_E_CORRUPT;
+        if (st == TSG_OK) sll = fse_init(W.ll, b), sof = fse_init(W.of, b), sml = fse_init(W.ml, b);
+      }
+    }
+    X.u[0] = st, X.u[1] = nseq;
+  }
+  wave_sync();
+  if (X.u[0] != TSG_OK) return int(X.u[0]);
+  const uint32_t nseq = X.u[1];
+  uint32_t lit_pos = 0;
+  for (uint32_t s0 = 0; s0 < nseq; s0 += kSeqBatch) {
+    const uint32_t nb = nseq - s0 < kSeqBatch ? nseq - s0 : kSeqBatch;
+    wave_sync();  // (the previous batch and X.u have been read)
+    if (lane == 0) {
+      uint32_t st = TSG_OK;
+      for (uint32_t i = 0; i < nb && st == TSG_OK; i++) {
+        const uint32_t ofc = W.of.sym[sof], mlc = W.ml.sym[sml], llc = W.ll.sym[sll];
+        if (ofc > 31 || mlc > uint32_t(kMLMax) || llc > uint32_t(kLLMax)) {
+          st = TSG_E_CORRUPT;
+          break;
+        }
+        const uint32_t ofv = (1u << ofc) + b.read(int(ofc));  // offset bits first, then match, then literal
+        const uint32_t ml = kMLBase[mlc] + b.read(kMLBits[mlc]);
+        const uint32_t ll = kLLBase[llc] + b.read(kLLBits[llc]);
+        FrameState &F = S.F;
+        uint32_t off;
+        if (ofv > 3) {
+          off = ofv - 3;
+          F.rep[2] = F.rep[1];
+          F.rep[1] = F.rep[0];
+          F.rep[0] = off;
+          ZDEV_STAT(if (off > g_zstat.max_off) g_zstat.max_off = off;)
+        } else {
+          ZDEV_STAT(g_zstat.repeats++;)
+          const uint32_t idx = ofv - 1 + (ll == 0 ? 1u : 0u);
+          if (idx == 0) {
+            off = F.rep[0];
+          } else {
+            off = idx == 1 ? F.rep[1] : idx == 2 ? F.rep[2] : F.rep[0] - 1;  // (no indexing by idx: F stays in registers)
+            if (idx > 1) F.rep[2] = F.rep[1];
+            F.rep[1] = F.rep[0];
+            F.rep[0] = off;
+          }
+        }
+        if (s0 + i + 1 < nseq) {  // states: literal length, match length, offset
+          sll = fse_update(W.ll, sll, b);
+          sml = fse_update(W.ml, sml, b);
+          sof = fse_update(W.of, sof, b);
+        }
+        X.seq[i] = SeqRec{ll, ml, off};
+      }
+      if (st == TSG_OK && s0 + nb == nseq && b.left() != 0) st = TSG_E_CORRUPT;
+      X.u[0] = st;
+    }
+    wave_sync();
+    if (X.u[0] != TSG_OK) return int(X.u[0]);
+    for (uint32_t i = 0; i < nb; i++) {
+      const uint32_t ll = wave_uniform(X.seq[i].ll), ml = wave_uniform(X.seq[i].ml), off = wave_uniform(X.seq[i].off);
+      const int st = wave_sequence(out, pos, cap, frame_start, W.lit, lit_pos, regen, ll, ml, off, S.settled, lane);
+      if (st) return st;
+    }
+  }
+  const uint32_t rest = regen - lit_pos;
+  if (rest > cap - pos) return TSG_E_CORRUPT;
+  for (uint32_t k = lane; k < rest; k += kLanes) out[pos + k] = W.lit[lit_pos + k];
+  pos += rest;
+  wave_sync();  // (W.lit and X are free for the next block)
+  return TSG_OK;
+}
+
+// the whole payload by one wave: as zstd_decode, every lane returns the same status and *len
+__device__ __forceinline__ int zstd_decode_wave(const uint8_t *p, uint32_t n, uint8_t *out, uint64_t cap, uint64_t &len, Work &W,
+                                       WaveWork &X, uint32_t lane) {
+  uint64_t pos = 0;
+  uint32_t s = 0;
+  if (lane == 0) W.huf.maxb = 0;
+  while (s < n) {
+    if (n - s < 4) return TSG_E_CORRUPT;
+    const uint32_t magic = uint32_t(p[s]) | uint32_t(p[s + 1]) << 8 | uint32_t(p[s + 2]) << 16 | uint32_t(p[s + 3]) << 24;
+    if ((magic & 0xFFFFFFF0u) == 0x184D2A50u) {  // skippable frame (3.1.2)
+      if (n - s < 8) return TSG_E_CORRUPT;
+      const uint32_t sz = uint32_t(p[s + 4]) | uint32_t(p[s + 5]) << 8 | uint32_t(p[s + 6]) << 16 | uint32_t(p[s + 7]) << 24;
+      if (sz > n - s - 8) return TSG_E_CORRUPT;
+      s += 8 + sz;
+      continue;
+    }
+    if (magic != 0xFD2FB528u) return TSG_E_CORRUPT;
+    uint64_t fcs;
+    bool csum;
+    int st = TSG_OK;
+    const uint32_t h = frame_header(p + s, n - s, fcs, csum, st);
+    if (!h) return st != TSG_OK ? st : TSG_E_CORRUPT;
+    s += h;
+    const uint64_t fstart = pos;
+    WaveState S{pos, FrameState{{1, 4, 8}, false, false, false}};
+    wave_sync();
+    if (lane == 0) W.huf.maxb = 0;
+    for (;;) {
+      if (n - s < 3) return TSG_E_CORRUPT;
+      const uint32_t bh = uint32_t(p[s]) | uint32_t(p[s + 1]) << 8 | uint32_t(p[s + 2]) << 16;
+      s += 3;
+      const uint32_t type = (bh >> 1) & 3, size = bh >> 3;
+      ZDEV_STAT(g_zstat.block[type]++;)
+      if (type == 0) {  // raw
+        if (size > n - s || size > cap - pos) return TSG_E_CORRUPT;
+        for (uint32_t k = lane; k < size; k += kLanes) out[pos + k] = p[s + k];
+        pos += size;
+        s += size;
+      } else if (type == 1) {  // RLE
+        if (n - s < 1 || size > cap - pos) return TSG_E_CORRUPT;
+        const uint8_t v = p[s];
+        for (uint32_t k = lane; k < size; k += kLanes) out[pos + k] = v;
+        pos += size;
+        s += 1;
+      } else if (type == 2) {
+        if (size > n - s || size > kMaxBlock) return TSG_E_CORRUPT;
+        const int r = block_compressed_wave(p + s, size, out, pos, cap, fstart, W, X, S, lane);
+        if (r) return r;
+        s += size;
+      } else {
+        return TSG_E_CORRUPT;
+      }
+      if (bh & 1) break;
+    }
+    if (fcs != ~0ull && pos - fstart != fcs) return TSG_E_CORRUPT;
+    if (csum) {  // lane 0 reads the frame back once its stores have completed
+      if (n - s < 4) return TSG_E_CORRUPT;
+      const uint32_t want = uint32_t(p[s]) | uint32_t(p[s + 1]) << 8 | uint32_t(p[s + 2]) << 16 | uint32_t(p[s + 3]) << 24;
+      wave_stores_done();
+      wave_sync();
+      if (lane == 0) X.u[0] = uint32_t(xxh64(out + fstart, pos - fstart)) == want ? 1u : 0u;
+      wave_sync();
+      if (!X.u[0]) return TSG_E_CORRUPT;
       s += 4;
     }
   }

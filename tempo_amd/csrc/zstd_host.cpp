@@ -2,6 +2,7 @@
 // loader (proto.cpp) decodes zstd data pages once at open (the v2 data default,
 // modules/storage/config.go:39-53; reference: klauspost/compress/zstd DecodeAll,
 // tempodb/encoding/v2/data_reader.go:111-117). findOne runs the same code on the GPU.
+#include <atomic>
 #include <cstdint>
 #include <cstring>
 #include <memory>
@@ -13,6 +14,7 @@ static inline int __clz(uint32_t x) { return x ? __builtin_clz(x) : 32; }
 #include "tsg.h"
 #define TSG_ZSTD_HOST
 #include "zstd_dev.hpp"
+#include "zstd_enc.hpp"
 
 namespace tsg {
 
@@ -33,6 +35,12 @@ int zstd_host_decode(const uint8_t *src, size_t n, std::vector<uint8_t> &out) {
   if (st != TSG_OK) return st;
   out.resize(len);
   return TSG_OK;
+}
+
+static std::atomic<uint32_t> g_zstd_flags{0};
+void zstd_writer_flags(uint32_t bits) { g_zstd_flags.store(bits); }
+void zstd_frame_encode(const uint8_t *src, size_t n, std::vector<uint8_t> &out) {
+  zenc::zstd_frame_encode(src, n, g_zstd_flags.load(), out);
 }
 
 }  // namespace tsg

@@ -41,6 +41,7 @@ ENC_LZ4_256K = 3
 ENC_LZ4_1M = 4
 ENC_LZ4_4M = 5  # "lz4"
 ENC_SNAPPY = 6
+ENC_ZSTD = 7
 ENC_NAMES = ["none", "gzip", "lz4-64k", "lz4-256k", "lz4-1M", "lz4", "snappy", "zstd", "s2"]  # backend.Encoding.String
 
 SEARCH_TIME_SCAN = 1  # tsg_search_opts.flags: HIP events around the scan kernel
@@ -161,7 +162,7 @@ EXPORTED = [
     "tsg_block_tag_values", "tsg_free", "tsg_search", "tsg_result_free", "tsg_kernel_times", "tsg_results_combine",
     "tsg_v2block_open", "tsg_v2block_close", "tsg_lookup_ids", "tsg_lookup_result_free", "tsg_find_ids",
     "tsg_find_result_free", "tsg_proto_block_open", "tsg_proto_block_close", "tsg_proto_block_info",
-    "tsg_proto_search", "tsg_proto_result_free", "tsg_go_parse", "tsg_write_v2_block",
+    "tsg_proto_search", "tsg_proto_result_free", "tsg_go_parse", "tsg_write_v2_block", "tsg_write_v2_block_pages",
     "tsg_write_search_block", "tsg_write_wal_search", "tsg_fb_search_entry", "tsg_fb_search_header", "tsg_synth_search_block",
     "tsg_synth_v2_block", "tsg_live_block_open_mem", "tsg_search_tags", "tsg_search_tag_values",
     "tsg_result_pack", "tsg_wire_merge", "tsg_search_batch", "tsg_debug_set",
@@ -238,6 +239,9 @@ def lib():
         L.tsg_proto_search.argtypes = [vp, vp, C.POINTER(_ProtoRequest), C.POINTER(C.POINTER(_ProtoResult))]
         L.tsg_proto_result_free.argtypes = [C.POINTER(_ProtoResult)]
         L.tsg_go_parse.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
+        L.tsg_write_v2_block_pages.argtypes = [C.c_char_p, vp, C.c_char_p, C.POINTER(C.c_uint64), C.c_size_t,
+                                               C.POINTER(C.c_uint64), C.c_char_p, C.POINTER(C.c_uint64), C.c_size_t,
+                                               C.c_int, C.c_char_p]
         L.tsg_write_v2_block.argtypes = [C.c_char_p, vp, C.c_char_p, C.POINTER(C.c_uint64), C.c_size_t, C.c_int,
                                          C.c_char_p, C.c_uint32]
         L.tsg_write_search_block.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_int, C.c_uint32]
@@ -849,7 +853,8 @@ _block_closes = [0]  # BackendSearchBlock closes so far
 
 def debug_set(name: str, value: int) -> None:
     """tsg_debug_set: process-wide test hooks ("res_torn": the next `value` resident posts are
-    written torn, then repaired; DESIGN.md §4. "lz4_writer_flags": checksum bits of the lz4 page
+    written torn, then repaired; DESIGN.md §4. "zstd_writer_flags": forced forms of the zstd page writer; "zstd_find_lane": 1 selects the
+    one-lane zstd page decoder of find; "lz4_writer_flags": checksum bits of the lz4 page
     writer, include/tsg.h)."""
     _check(lib().tsg_debug_set(name.encode(), value))
 
@@ -1088,6 +1093,35 @@ def write_v2_block(path: str, ids, objects: Sequence[bytes], encoding: int = 0, 
     offs = (C.c_uint64 * len(off))(*off)
     _check(lib().tsg_write_v2_block(path.encode(), ids.ctypes.data, blob, offs, ids.shape[0], encoding,
                                     data_encoding.encode(), index_downsample_bytes))
+
+
+def write_v2_block_pages(path: str, ids, objects: Sequence[bytes], page_first: Sequence[int], payloads: Sequence[bytes],
+                         encoding: int, data_encoding: str = "v2"):
+    """tsg_write_v2_block_pages: a v2 block whose data pages the caller has encoded already: payloads[p]
+    decodes (at `encoding`) to marshal_objects of ids page_first[p] .. page_first[p + 1] - 1."""
+    import numpy as np
+    ids = np.ascontiguousarray(ids, dtype=np.uint8).reshape(-1, 16)
+    assert len(objects) == ids.shape[0] and len(page_first) == len(payloads)
+
+    def packed(parts):
+        off = [0]
+        for o in parts:
+            off.append(off[-1] + len(o))
+        return b"".join(parts), (C.c_uint64 * len(off))(*off)
+    blob, offs = packed(objects)
+    pblob, poffs = packed(payloads)
+    first = (C.c_uint64 * len(page_first))(*page_first)
+    _check(lib().tsg_write_v2_block_pages(path.encode(), ids.ctypes.data, blob, offs, ids.shape[0], first, pblob, poffs,
+                                          len(payloads), encoding, data_encoding.encode()))
+
+
+def marshal_objects(ids, objects: Sequence[bytes]) -> bytes:
+    """The decoded bytes of a v2 data page: [u32 total][u32 id length][id][object] per object (object.go:25-48)."""
+    out = bytearray()
+    for i, o in zip(ids, objects):
+        i = bytes(i)
+        out += struct.pack("<II", len(o) + len(i) + 8, len(i)) + i + o
+    return bytes(out)
 
 
 def go_parse(kind: str, s) -> tuple:
