@@ -166,15 +166,7 @@ void read_data_page(const uint8_t *file, size_t flen, const IndexRecord &r, int 
   const uint8_t *hdr, *payload;
   size_t pl;
   unmarshal_page(file + r.start, r.length, 0, hdr, payload, pl);
-  if (enc == 0) out.assign(payload, payload + pl);
-  else if (enc == 6) snappy_framed_decode(payload, pl, out);
-  else if (enc == 7) {
-    const int st = zstd_host_decode(payload, pl, out);
-    if (st != TSG_OK) fail(st, "zstd page decode failed");
-  } else if (is_lz4_encoding(enc)) {
-    const int st = lz4_host_decode(payload, pl, out);
-    if (st != TSG_OK) fail(st, "lz4 page decode failed");
-  } else fail(TSG_E_UNSUPPORTED_ENCODING, std::string("unsupported page encoding ") + encoding_name(enc));
+  page_decode(enc, payload, pl, out);
 }
 
 // ---- page parse ---------------------------------------------------------------------------
@@ -1253,8 +1245,7 @@ void decode_search_block(const uint8_t *meta, size_t meta_len, bool meta_present
   hb.has_meta = true;
   hb.meta = parse_search_meta(meta, meta_len);
   if (hb.meta.version != "v2") fail(TSG_E_UNSUPPORTED_ENCODING, "unsupported search block version " + hb.meta.version);
-  if (hb.meta.encoding != 0 && hb.meta.encoding != 6 && hb.meta.encoding != 7 && !is_lz4_encoding(hb.meta.encoding))
-    fail(TSG_E_UNSUPPORTED_ENCODING, std::string("search encoding not supported: ") + encoding_name(hb.meta.encoding));
+  require_page_encoding(hb.meta.encoding, std::string("search encoding not supported: ") + encoding_name(hb.meta.encoding));
   hb.header = std::move(header);
   {
     FbTable h = FbTable::root(hb.header.data(), hb.header.size());
@@ -1497,8 +1488,7 @@ void decode_wal_search_block(const uint8_t *file, size_t len, int enc, HostBlock
   hb.streaming = true;
   hb.meta.version = "v2";
   hb.meta.encoding = enc;
-  if (enc != 0 && enc != 6 && enc != 7 && !is_lz4_encoding(enc))
-    fail(TSG_E_UNSUPPORTED_ENCODING, std::string("search encoding not supported: ") + encoding_name(enc));
+  require_page_encoding(enc, std::string("search encoding not supported: ") + encoding_name(enc));
   struct Rec {
     std::string id;
     std::vector<uint8_t> obj;
@@ -1515,11 +1505,7 @@ void decode_wal_search_block(const uint8_t *file, size_t len, int enc, HostBlock
       const uint8_t *hdr, *payload;
       size_t pl;
       unmarshal_page(file + off, total, 0, hdr, payload, pl);
-      if (enc == 0) buf.assign(payload, payload + pl);
-      else if (enc == 6) snappy_framed_decode(payload, pl, buf);
-      else if (enc == 7) {
-        if (const int st = zstd_host_decode(payload, pl, buf); st != TSG_OK) fail(st, "zstd page decode failed");
-      } else if (const int st = lz4_host_decode(payload, pl, buf); st != TSG_OK) fail(st, "lz4 page decode failed");
+      page_decode(enc, payload, pl, buf);
       // exactly one object per page: [u32 total][u32 idLen][id][obj], then EOF
       if (buf.size() < 8) fail(TSG_E_CORRUPT, "object header truncated");
       const uint32_t ot = le32(buf.data()), il = le32(buf.data() + 4);

@@ -16,6 +16,16 @@
 #include <sys/types.h>
 #include <strings.h>
 
+// The codec headers of find.hip built for the host: the loaders decode pages with the same parsers.
+#define __device__
+#define __forceinline__ inline
+#define TSG_LZ4_HOST
+#define TSG_SNAPPY_HOST
+#include "lz4_dev.hpp"
+#include "snappy_dev.hpp"
+#undef __device__
+#undef __forceinline__
+
 namespace tsg {
 
 uint32_t json_u32(std::string_view v, const char *field) {
@@ -157,10 +167,8 @@ uint32_t crc32c(const uint8_t *p, size_t n) {
   while (n--) c = g_crc[0][(c ^ *p++) & 0xff] ^ (c >> 8);
   return ~c;
 }
-static inline uint32_t snappy_mask(uint32_t c) { return ((c >> 15) | (c << 17)) + 0xa282ead8u; }
 
-// ---- snappy -----------------------------------------------------------------
-static constexpr size_t kMaxBlock = 65536, kMaxEnc = 76490;
+// ---- snappy: the framing is snappy_dev.hpp's, shared with the device -------------------
 
 static void snappy_block_decode(const uint8_t *src, size_t sl, uint8_t *dst, size_t dl) {
   size_t d = 0, s = 0;
@@ -231,86 +239,34 @@ static void snappy_block_decode(const uint8_t *src, size_t sl, uint8_t *dst, siz
   if (d != dl) fail(TSG_E_CORRUPT, "snappy: short block");
 }
 
-// Decoded size of a framed stream, from its chunk headers (no checks beyond what reading them
-// needs: stops at the first chunk it cannot read; the decode below does the checking)
-static size_t snappy_framed_size(const uint8_t *src, size_t n) {
-  size_t s = 0, total = 0;
-  while (n - s >= 4) {
-    const uint8_t ct = src[s];
-    const size_t cl = size_t(src[s + 1]) | (size_t(src[s + 2]) << 8) | (size_t(src[s + 3]) << 16);
-    s += 4;
-    if (cl > n - s) break;
-    const uint8_t *b = src + s;
-    s += cl;
-    if (ct == 0x00) {
-      uint64_t v = 0;
-      int shift = 0;
-      for (size_t i = 0; 4 + i < cl && i < 10; i++) {
-        v |= uint64_t(b[4 + i] & 0x7f) << shift;
-        if (b[4 + i] < 0x80) {
-          total += std::min<uint64_t>(v, kMaxBlock);
-          break;
-        }
-        shift += 7;
-      }
-    } else if (ct == 0x01 && cl >= 4) {
-      total += std::min<size_t>(cl - 4, kMaxBlock);
-    }
-  }
-  return total;
-}
+static const char *const kWalkErr[] = {"truncated chunk header", "missing stream identifier", "chunk too large",
+                                       "truncated chunk",        "chunk without checksum",    "bad varint",
+                                       "block too large",        "bad stream identifier",     "reserved unskippable chunk"};
+static_assert(sizeof kWalkErr / sizeof *kWalkErr == -snapdev::ChunkWalk::kReserved, "one text per ChunkWalk::Err, in its order");
 
 void snappy_framed_decode(const uint8_t *src, size_t n, std::vector<uint8_t> &out) {
   out.clear();
+  if (n > 0xffffffffu) fail(TSG_E_CORRUPT, "snappy: stream too large");
   // one allocation (and one zero fill) for the whole stream instead of a growing vector; the
-  // chunk headers are not checked yet, so the reserve is capped (a corrupt header can claim
-  // 64 KiB for an 11-byte chunk) and the vector grows past it if it must
-  out.reserve(std::min<size_t>(snappy_framed_size(src, n), 16 * n + (size_t(1) << 20)));
-  size_t s = 0;
-  bool hdr = false;
-  while (s < n) {
-    if (n - s < 4) fail(TSG_E_CORRUPT, "snappy: truncated chunk header");
-    uint8_t ct = src[s];
-    size_t cl = size_t(src[s + 1]) | (size_t(src[s + 2]) << 8) | (size_t(src[s + 3]) << 16);
-    s += 4;
-    if (!hdr) {
-      if (ct != 0xff) fail(TSG_E_CORRUPT, "snappy: missing stream identifier");
-      hdr = true;
+  // blocks are not decoded yet, so the reserve is capped (a corrupt header can claim 64 KiB for
+  // an 11-byte chunk) and the vector grows past it if it must
+  uint64_t total = 0;
+  snapdev::snappy_size(src, uint32_t(n), total);
+  out.reserve(std::min<size_t>(total, 16 * n + (size_t(1) << 20)));
+  snapdev::ChunkWalk w;
+  for (;;) {
+    const int r = w.next(src, uint32_t(n));
+    if (r < 0) fail(TSG_E_CORRUPT, std::string("snappy: ") + kWalkErr[-r - 1]);
+    if (r == 0) break;
+    const size_t base = out.size();
+    if (w.type == 0x00) {
+      out.resize(base + w.ulen);
+      snappy_block_decode(src + w.block, w.data + w.size - w.block, out.data() + base, w.ulen);
+    } else {
+      out.insert(out.end(), src + w.data, src + w.data + w.size);
     }
-    if (cl > kMaxEnc + 4) fail(TSG_E_CORRUPT, "snappy: chunk too large");
-    if (cl > n - s) fail(TSG_E_CORRUPT, "snappy: truncated chunk");
-    const uint8_t *b = src + s;
-    s += cl;
-    if (ct == 0x00 || ct == 0x01) {
-      if (cl < 4) fail(TSG_E_CORRUPT, "snappy: chunk without checksum");
-      uint32_t csum = le32(b);
-      size_t base = out.size();
-      if (ct == 0x00) {
-        // varint decoded length (decode.go:30-43)
-        uint64_t v = 0;
-        size_t i = 0;
-        int shift = 0;
-        for (;; i++) {
-          if (4 + i >= cl || i >= 10) fail(TSG_E_CORRUPT, "snappy: bad varint");
-          uint8_t c = b[4 + i];
-          v |= uint64_t(c & 0x7f) << shift;
-          if (c < 0x80) break;
-          shift += 7;
-        }
-        if (v > kMaxBlock) fail(TSG_E_CORRUPT, "snappy: block too large");
-        out.resize(base + v);
-        snappy_block_decode(b + 5 + i, cl - 5 - i, out.data() + base, v);
-      } else {
-        if (cl - 4 > kMaxBlock) fail(TSG_E_CORRUPT, "snappy: block too large");
-        out.insert(out.end(), b + 4, b + cl);
-      }
-      if (snappy_mask(crc32c(out.data() + base, out.size() - base)) != csum)
-        fail(TSG_E_CORRUPT, "snappy: checksum mismatch");
-    } else if (ct == 0xff) {
-      if (cl != 6 || std::memcmp(b, "sNaPpY", 6) != 0) fail(TSG_E_CORRUPT, "snappy: bad stream identifier");
-    } else if (ct <= 0x7f) {
-      fail(TSG_E_CORRUPT, "snappy: reserved unskippable chunk");
-    }
+    if (snapdev::crc_mask(crc32c(out.data() + base, out.size() - base)) != w.crc)
+      fail(TSG_E_CORRUPT, "snappy: checksum mismatch");
   }
 }
 
@@ -394,10 +350,10 @@ void snappy_framed_encode(const uint8_t *src, size_t n, std::vector<uint8_t> &ou
   static const uint8_t magic[10] = {0xff, 0x06, 0x00, 0x00, 's', 'N', 'a', 'P', 'p', 'Y'};
   out.insert(out.end(), magic, magic + 10);
   std::vector<uint8_t> comp;
-  for (size_t off = 0; off < n; off += kMaxBlock) {
-    size_t len = n - off < kMaxBlock ? n - off : kMaxBlock;
+  for (size_t off = 0; off < n; off += snapdev::kMaxBlock) {
+    size_t len = std::min<size_t>(n - off, snapdev::kMaxBlock);
     const uint8_t *u = src + off;
-    uint32_t csum = snappy_mask(crc32c(u, len));
+    uint32_t csum = snapdev::crc_mask(crc32c(u, len));
     snappy_block_encode(u, len, comp);
     bool use_comp = comp.size() < len - len / 8;
     size_t cl = 4 + (use_comp ? comp.size() : len);
@@ -672,22 +628,11 @@ void prof_add(const char *name, double us) {
   t.rows.push_back({name, {us}});
 }
 
-}  // namespace tsg
-
 // ---- lz4 frames ---------------------------------------------------------------------------
-// The frame decoder of lz4_dev.hpp built for the host (the loaders decode lz4 pages at open;
-// findOne runs the same parser on the GPU), and the writer's encoder: a greedy hash-table
+// The frame decoder of lz4_dev.hpp on the host, and the writer's encoder: a greedy hash-table
 // block compressor inside the frame the reference Writer emits (tempodb/encoding/v2/
 // pool.go:220-238; pierrec/lz4/v4 writer.go, internal/lz4stream). Any valid block decodes
 // identically; byte-identity with the Go compressor is not a goal.
-#define __device__
-#define __forceinline__ inline
-#define TSG_LZ4_HOST
-#include "lz4_dev.hpp"
-#undef __device__
-#undef __forceinline__
-
-namespace tsg {
 
 int lz4_host_decode(const uint8_t *src, size_t n, std::vector<uint8_t> &out) {
   out.clear();
@@ -751,7 +696,7 @@ static void lz4_block_encode(const uint8_t *src, size_t n, std::vector<uint8_t> 
 }
 
 void lz4_frame_encode(const uint8_t *src, size_t n, int enc, std::vector<uint8_t> &out) {
-  if (!is_lz4_encoding(enc)) fail(TSG_E_INVALID, "lz4_frame_encode: not an lz4 encoding");
+  if (page_codec(enc) != PageCodec::Lz4) fail(TSG_E_INVALID, "lz4_frame_encode: not an lz4 encoding");
   const uint32_t bits = g_writer_flags.load();
   const bool bsum = (bits & 5) != 0, bsum_stored = (bits & 4) != 0, csum = (bits & 2) != 0;
   const uint32_t idx = uint32_t(enc) + 2;  // lz4-64k -> 4 ... lz4 (4 MiB) -> 7
@@ -778,6 +723,35 @@ void lz4_frame_encode(const uint8_t *src, size_t n, int enc, std::vector<uint8_t
   }
   put_le32(out, 0);  // end mark
   if (csum) put_le32(out, lz4dev::xxh32(src, n));
+}
+
+// ---- page codecs: the one dispatch on backend.Encoding of the host ------------------------
+void require_page_encoding(int enc, const std::string &msg) {
+  if (page_codec(enc) == PageCodec::Unsupported) fail(TSG_E_UNSUPPORTED_ENCODING, msg);
+}
+
+void page_decode(int enc, const uint8_t *payload, size_t len, std::vector<uint8_t> &out) {
+  auto ok = [](int st, const char *msg) { if (st != TSG_OK) fail(st, msg); };  // the status-returning decoders
+  switch (page_codec(enc)) {
+    case PageCodec::None: out.assign(payload, payload + len); break;
+    case PageCodec::Snappy: snappy_framed_decode(payload, len, out); break;
+    case PageCodec::Zstd: ok(zstd_host_decode(payload, len, out), "zstd page decode failed"); break;
+    case PageCodec::Lz4: ok(lz4_host_decode(payload, len, out), "lz4 page decode failed"); break;
+    case PageCodec::Unsupported:
+      fail(TSG_E_UNSUPPORTED_ENCODING, std::string("unsupported page encoding ") + encoding_name(enc));
+  }
+}
+
+void page_encode(int enc, const std::vector<uint8_t> &objects, std::vector<uint8_t> &payload) {
+  payload.clear();
+  switch (page_codec(enc)) {
+    case PageCodec::None: payload = objects; break;
+    case PageCodec::Snappy: snappy_framed_encode(objects.data(), objects.size(), payload); break;
+    case PageCodec::Zstd: zstd_frame_encode(objects.data(), objects.size(), payload); break;
+    case PageCodec::Lz4: lz4_frame_encode(objects.data(), objects.size(), enc, payload); break;
+    case PageCodec::Unsupported:
+      fail(TSG_E_UNSUPPORTED_ENCODING, std::string("writer: unsupported encoding ") + encoding_name(enc));
+  }
 }
 
 }  // namespace tsg

@@ -93,8 +93,22 @@ void snappy_framed_decode(const uint8_t *src, size_t n, std::vector<uint8_t> &ou
 // compressed unless the saving is < 12.5 % (encode.go:218-235).
 void snappy_framed_encode(const uint8_t *src, size_t n, std::vector<uint8_t> &out);
 
+// ---- page codecs: what a backend.Encoding number means (tempodb/backend/encoding.go:12-22) ----
+enum class PageCodec { None, Snappy, Lz4, Zstd, Unsupported };  // Unsupported: gzip, s2, unknown numbers
+constexpr PageCodec page_codec(int enc) {  // (plain constexpr: device code calls it too)
+  return enc == 0                ? PageCodec::None
+         : enc == 6              ? PageCodec::Snappy
+         : enc == 7              ? PageCodec::Zstd
+         : (enc >= 2 && enc <= 5) ? PageCodec::Lz4  // lz4-64k / -256k / -1M / lz4
+                                  : PageCodec::Unsupported;
+}
+// fails with TSG_E_UNSUPPORTED_ENCODING and `msg` unless enc is one of the four codecs
+void require_page_encoding(int enc, const std::string &msg);
+// One v2 page payload decoded / encoded at enc; fails with the codec's status.
+void page_decode(int enc, const uint8_t *payload, size_t len, std::vector<uint8_t> &out);
+void page_encode(int enc, const std::vector<uint8_t> &objects, std::vector<uint8_t> &payload);
+
 // ---- lz4 frames (github.com/pierrec/lz4/v4 v4.1.12 wire format) -----------
-inline bool is_lz4_encoding(int enc) { return enc >= 2 && enc <= 5; }  // lz4-64k / -256k / -1M / lz4
 // Decode the one frame of a v2 page payload (lz4_dev.hpp built for the host): TSG_OK or the error.
 int lz4_host_decode(const uint8_t *src, size_t n, std::vector<uint8_t> &out);
 // Encode like lz4.Writer with the options of tempodb/encoding/v2/pool.go:220-238: independent
@@ -105,7 +119,8 @@ void lz4_frame_encode(const uint8_t *src, size_t n, int enc, std::vector<uint8_t
 // defines them (over the stored bytes; wins over 1)
 void lz4_writer_flags(uint32_t bits);
 
-// ---- zstd frames (RFC 8878; zstd_enc.hpp, built in zstd_host.cpp) ------------------------------
+// ---- zstd frames (RFC 8878; zstd_dev.hpp and zstd_enc.hpp, built in zstd_host.cpp) -------------
+int zstd_host_decode(const uint8_t *src, size_t n, std::vector<uint8_t> &out);
 // One frame holding the page: a window over all of it, the content size, blocks <= 128 KiB.
 void zstd_frame_encode(const uint8_t *src, size_t n, std::vector<uint8_t> &out);
 // test hook (tsg_debug_set "zstd_writer_flags"): the zenc flag bits of zstd_enc.hpp (1 content

@@ -6,20 +6,24 @@
 //   dataReader.Read (one record)   tempodb/encoding/v2/data_reader.go:45-125
 //   page framing                   tempodb/encoding/v2/page.go:28-57
 //   object framing / iterator      tempodb/encoding/v2/object.go:82-113, iterator.go
-//   snappy framed stream           vendor/github.com/golang/snappy/decode.go:121-232,
+//   snappy framed stream           vendor/github.com/golang/snappy/decode.go:121-232, snappy_dev.hpp;
 //                                  block format decode_other.go:41-102
 //   lz4 frame (lz4-64k .. lz4)     vendor/github.com/pierrec/lz4/v4/reader.go, lz4_dev.hpp
+//   zstd frame                     RFC 8878, zstd_dev.hpp
 //
 // Per batch: (1) the distinct (block, record) pages of the lookup hits, (2) a size pass
 // (one lane per page walks the frame headers), (3) decode: one wave per page, each
-// snappy chunk (<= 64 KiB decoded) staged and decoded in LDS with all 64 lanes (tags
+// snappy chunk (<= 64 KiB decoded; snapdev::ChunkWalk gives the chunks, as in the size pass)
+// staged and decoded in LDS with all 64 lanes (snap_block_wave: tags
 // parsed in lockstep, literal and match bytes copied in parallel: a match of offset o
 // is periodic, byte j = out[d - o + j % o], so no lane waits on another), CRC32C of the
 // chunk per lane segment and combined, then written to HBM coalesced; (4) object scan:
 // one wave per page walks the objects through 64 KiB LDS windows and the lanes compare
 // each object id against the page's pending ids (first exact match, as findOne);
 // (5) the found objects are gathered into one arena for the copy back.
-// Encodings: none, snappy, zstd (zstd_dev.hpp; find_decode_zstd_wave_kernel: one wave per page,
+// Encodings (page_codec(), common.hpp; the three codec headers have one shape: constants, a frame
+// walker and a size function, built for the host too, and this file holds their wave-level
+// kernels): none, snappy, zstd (zstd_dev.hpp; find_decode_zstd_wave_kernel: one wave per page,
 // step (3'z) below; the older one-lane kernel behind tsg_debug_set "zstd_find_lane") and the four lz4 ones
 // (lz4_dev.hpp parses the frame; find_decode_lz4_kernel: one wave per page, each block
 // decoded through a 64 KiB output ring in LDS, step (3'') below); gzip / s2 report
@@ -33,6 +37,7 @@
 
 #include "devctx.hpp"
 #include "lz4_dev.hpp"
+#include "snappy_dev.hpp"
 #include "zstd_dev.hpp"
 
 namespace tsg {
@@ -45,14 +50,11 @@ struct FindPage {
   uint32_t out_len;    // decoded size (size pass)
   int32_t status;      // TSG_OK or the page's error
   uint32_t hit0, nhit; // this page's pending ids: hits [hit0, hit0 + nhit)
+  constexpr PageCodec codec() const { return page_codec(int(enc)); }
 };
 
-constexpr uint32_t kSnapMaxBlock = 65536, kSnapMaxChunk = 76490 + 4;  // decode.go: maxBlockSize, buf size
-constexpr uint32_t kFindWindow = 65536;                               // object scan window (LDS)
-
-__device__ __forceinline__ uint32_t g_le32(const uint8_t *p) {
-  return uint32_t(p[0]) | uint32_t(p[1]) << 8 | uint32_t(p[2]) << 16 | uint32_t(p[3]) << 24;
-}
+constexpr uint32_t kFindWindow = 65536;  // object scan window (LDS)
+using lz4dev::rd32;                      // the file's one little-endian 32-bit read
 
 // (2) decoded size of each page; framing errors are recorded here
 extern "C" __global__ void __launch_bounds__(256) find_size_kernel(FindPage *pages, uint32_t npages) {
@@ -61,95 +63,27 @@ extern "C" __global__ void __launch_bounds__(256) find_size_kernel(FindPage *pag
   FindPage &P = pages[i];
   P.out_len = 0;
   // unmarshalPageFromBytes with the data header (length 0) (page.go:28-57)
-  if (P.len < 6 || g_le32(P.src) != P.len || (uint32_t(P.src[4]) | uint32_t(P.src[5]) << 8) != 0) {
+  if (P.len < 6 || rd32(P.src) != P.len || (uint32_t(P.src[4]) | uint32_t(P.src[5]) << 8) != 0) {
     P.status = TSG_E_CORRUPT;
     return;
   }
   const uint8_t *b = P.src + 6;
   const uint32_t n = P.len - 6;
-  if (P.enc == 0) {  // EncNone
-    P.out_len = n;
-    P.status = TSG_OK;
-    return;
+  uint64_t sz = n;
+  switch (P.codec()) {
+    case PageCodec::None: P.status = TSG_OK; break;
+    case PageCodec::Snappy: P.status = snapdev::snappy_size(b, n, sz); break;  // the chunks' declared lengths
+    case PageCodec::Lz4: P.status = lz4dev::lz4_size(b, n, sz); break;  // the content size, or the blocks' tokens walked
+    case PageCodec::Zstd: P.status = zdev::zstd_size(b, n, sz); break;  // frame content sizes (or block bounds)
+    case PageCodec::Unsupported: P.status = TSG_E_UNSUPPORTED_ENCODING; break;
   }
-  if (P.enc == 7) {  // zstd: frame content sizes (or block bounds)
-    uint64_t sz = 0;
-    P.status = zdev::zstd_size(b, n, sz);
-    P.out_len = P.status == TSG_OK ? uint32_t(sz) : 0;
-    return;
-  }
-  if (P.enc >= 2 && P.enc <= 5) {  // lz4: the content size, or the blocks' tokens walked
-    uint64_t sz = 0;
-    P.status = lz4dev::lz4_size(b, n, sz);
-    P.out_len = P.status == TSG_OK ? uint32_t(sz) : 0;
-    return;
-  }
-  if (P.enc != 6) {
-    P.status = TSG_E_UNSUPPORTED_ENCODING;
-    return;
-  }
-  uint64_t total = 0;
-  uint32_t s = 0;
-  bool hdr = false;
-  while (s < n) {
-    if (n - s < 4) {
-      P.status = TSG_E_CORRUPT;
-      return;
-    }
-    const uint32_t ct = b[s], cl = uint32_t(b[s + 1]) | uint32_t(b[s + 2]) << 8 | uint32_t(b[s + 3]) << 16;
-    s += 4;
-    if (!hdr && ct != 0xff) {
-      P.status = TSG_E_CORRUPT;
-      return;
-    }
-    hdr = true;
-    if (cl > kSnapMaxChunk || cl > n - s) {
-      P.status = TSG_E_CORRUPT;
-      return;
-    }
-    if (ct == 0x00) {  // compressed: [crc][varint decoded length][block]
-      uint64_t v = 0;
-      uint32_t k = 0;
-      for (int shift = 0;; shift += 7, k++) {
-        if (4 + k >= cl || k >= 5) {
-          P.status = TSG_E_CORRUPT;
-          return;
-        }
-        const uint32_t c = b[s + 4 + k];
-        v |= uint64_t(c & 0x7f) << shift;
-        if (c < 0x80) break;
-      }
-      if (v > kSnapMaxBlock) {
-        P.status = TSG_E_CORRUPT;
-        return;
-      }
-      total += v;
-    } else if (ct == 0x01) {
-      if (cl < 4 || cl - 4 > kSnapMaxBlock) {
-        P.status = TSG_E_CORRUPT;
-        return;
-      }
-      total += cl - 4;
-    } else if (ct == 0xff) {
-      const char *id = "sNaPpY";
-      bool ok = cl == 6;
-      for (int q = 0; q < 6 && ok; q++) ok = b[s + q] == uint8_t(id[q]);
-      if (!ok) {
-        P.status = TSG_E_CORRUPT;
-        return;
-      }
-    } else if (ct <= 0x7f) {  // reserved unskippable
-      P.status = TSG_E_CORRUPT;
-      return;
-    }
-    s += cl;
-  }
-  if (total >= (1ull << 31)) {
-    P.status = TSG_E_UNSUPPORTED;
-    return;
-  }
-  P.out_len = uint32_t(total);
-  P.status = TSG_OK;
+  P.out_len = P.status == TSG_OK ? uint32_t(sz) : 0;
+}
+
+// a page's payload (behind the 6-byte page header the size pass checked) and where it decodes to
+struct PageIO { const uint8_t *b; uint32_t n; uint8_t *out; };
+__device__ __forceinline__ PageIO page_io(const FindPage &P, uint8_t *arena) {
+  return PageIO{P.src + 6, P.len - 6, arena + P.out_off};
 }
 
 struct CrcArgs {
@@ -159,137 +93,135 @@ struct CrcArgs {
 
 // (3) one wave per page
 constexpr int kFindThreads = 64;
+// one staged snappy block cbuf[t .. bl) -> obuf[0 .. ulen), the tags parsed in lockstep (every
+// value that steers control is wave-uniform); decode_other.go:41-102
+__device__ int32_t snap_block_wave(const uint8_t *cbuf, uint32_t t, uint32_t bl, uint8_t *obuf, uint32_t ulen,
+                                   int lane) {
+  int32_t status = TSG_OK;
+  uint32_t d = 0;
+  while (t < bl) {
+    const uint32_t tag = cbuf[t];
+    uint32_t len, off = 0;
+    if ((tag & 3) == 0) {  // literal
+      uint32_t x = tag >> 2;
+      if (x < 60) {
+        t += 1;
+      } else {
+        const uint32_t nb = x - 59;
+        if (t + 1 + nb > bl) { status = TSG_E_CORRUPT; break; }
+        x = 0;
+        for (uint32_t q = 0; q < nb; q++) x |= uint32_t(cbuf[t + 1 + q]) << (8 * q);
+        t += 1 + nb;
+      }
+      len = x + 1;
+      if (len == 0 || len > bl - t || len > ulen - d) { status = TSG_E_CORRUPT; break; }
+      for (uint32_t j = lane; j < len; j += kFindThreads) obuf[d + j] = cbuf[t + j];
+      t += len;
+      d += len;
+      continue;
+    }
+    if ((tag & 3) == 1) {
+      if (t + 2 > bl) { status = TSG_E_CORRUPT; break; }
+      len = 4 + ((tag >> 2) & 7);
+      off = ((tag & 0xe0) << 3) | cbuf[t + 1];
+      t += 2;
+    } else if ((tag & 3) == 2) {
+      if (t + 3 > bl) { status = TSG_E_CORRUPT; break; }
+      len = 1 + (tag >> 2);
+      off = uint32_t(cbuf[t + 1]) | uint32_t(cbuf[t + 2]) << 8;
+      t += 3;
+    } else {
+      if (t + 5 > bl) { status = TSG_E_CORRUPT; break; }
+      len = 1 + (tag >> 2);
+      off = uint32_t(cbuf[t + 1]) | uint32_t(cbuf[t + 2]) << 8 | uint32_t(cbuf[t + 3]) << 16 |
+            uint32_t(cbuf[t + 4]) << 24;
+      t += 5;
+    }
+    if (off == 0 || off > d || len > ulen - d) { status = TSG_E_CORRUPT; break; }
+    // LZ77 copy: out[d + j] = out[d - off + j % off] (periodic when off < len)
+    if (off >= len) {
+      for (uint32_t j = lane; j < len; j += kFindThreads) obuf[d + j] = obuf[d - off + j];
+    } else {
+      for (uint32_t j = lane; j < len; j += kFindThreads) obuf[d + j] = obuf[d - off + j % off];
+    }
+    d += len;
+  }
+  if (status == TSG_OK && d != ulen) status = TSG_E_CORRUPT;
+  return status;
+}
+
+// CRC-32C of obuf[0 .. ulen), ulen <= 64 KiB, on every lane: 1 KiB per lane, combined on lane 0
+__device__ uint32_t wave_crc32c(const uint8_t *obuf, uint32_t ulen, const uint32_t *tab, uint32_t *lane_crc,
+                                const CrcArgs *crc, int lane) {
+  uint32_t r = 0;  // raw register from state 0
+  const uint32_t lo = uint32_t(lane) * 1024, hi = min(ulen, lo + 1024);
+  for (uint32_t i = lo; i < hi; i++) r = tab[(r ^ obuf[i]) & 0xff] ^ (r >> 8);
+  lane_crc[lane] = r;
+  __syncthreads();
+  if (lane == 0) {
+    uint32_t acc = 0xffffffffu;
+    const uint32_t nseg = (ulen + 1023) / 1024;
+    for (uint32_t g = 0; g < nseg; g++) {
+      const uint32_t sl = min(ulen - g * 1024, 1024u);
+      uint32_t z = 0;
+      if (sl == 1024) {  // advance by 1024 zero bytes: linear map, precomputed columns
+        for (int bb = 0; bb < 32; bb++)
+          if ((acc >> bb) & 1u) z ^= crc->z1024[bb];
+      } else {
+        z = acc;
+        for (uint32_t i = 0; i < sl; i++) z = tab[z & 0xff] ^ (z >> 8);
+      }
+      acc = z ^ lane_crc[g];
+    }
+    lane_crc[0] = ~acc;
+  }
+  __syncthreads();
+  const uint32_t c = lane_crc[0];
+  __syncthreads();
+  return c;
+}
+
 extern "C" __global__ void __launch_bounds__(kFindThreads) find_decode_kernel(FindPage *pages, uint8_t *arena,
                                                                             const CrcArgs *crc) {
-  __shared__ uint8_t cbuf[kSnapMaxChunk + 8];
-  __shared__ uint8_t obuf[kSnapMaxBlock + 8];
+  __shared__ uint8_t cbuf[snapdev::kMaxChunk + 8];
+  __shared__ uint8_t obuf[snapdev::kMaxBlock + 8];
   __shared__ uint32_t tab[256];
   __shared__ uint32_t lane_crc[kFindThreads];
   const int lane = threadIdx.x;
   FindPage &P = pages[blockIdx.x];
-  if (P.status != TSG_OK || (P.enc != 0 && P.enc != 6)) return;  // (zstd, lz4 pages: their own kernels)
+  const PageCodec codec = P.codec();
+  if (P.status != TSG_OK || (codec != PageCodec::None && codec != PageCodec::Snappy)) return;  // (zstd, lz4: their own kernels)
   for (int i = lane; i < 256; i += kFindThreads) tab[i] = crc->table[i];
-  const uint8_t *b = P.src + 6;
-  const uint32_t n = P.len - 6;
-  uint8_t *out = arena + P.out_off;
-  if (P.enc == 0) {
+  const auto [b, n, out] = page_io(P, arena);
+  if (codec == PageCodec::None) {
     for (uint32_t i = lane; i < n; i += kFindThreads) out[i] = b[i];
     return;
   }
   __syncthreads();
-  uint32_t s = 0, pos = 0;
+  snapdev::ChunkWalk w;  // (the size pass accepted the framing already)
+  uint32_t pos = 0;
   int32_t status = TSG_OK;
-  while (s + 4 <= n && status == TSG_OK) {
-    const uint32_t ct = b[s], cl = uint32_t(b[s + 1]) | uint32_t(b[s + 2]) << 8 | uint32_t(b[s + 3]) << 16;
-    s += 4;  // (framing checked by the size pass)
-    if (ct != 0x00 && ct != 0x01) {
-      s += cl;
-      continue;
+  while (status == TSG_OK) {
+    const int r = w.next(b, n);
+    if (r <= 0) {
+      if (r < 0) status = TSG_E_CORRUPT;
+      break;
     }
-    const uint32_t want = g_le32(b + s);
-    uint32_t ulen = 0;
-    if (ct == 0x01) {  // uncompressed chunk: copy into obuf for the checksum
-      ulen = cl - 4;
-      for (uint32_t i = lane; i < ulen; i += kFindThreads) obuf[i] = b[s + 4 + i];
+    const uint32_t ulen = w.ulen;
+    if (w.type == 0x01) {  // uncompressed chunk: copy into obuf for the checksum
+      for (uint32_t i = lane; i < ulen; i += kFindThreads) obuf[i] = b[w.data + i];
     } else {
       // stage the compressed block, then decode it in lockstep
-      const uint32_t bl = cl - 4;
-      for (uint32_t i = lane; i < bl; i += kFindThreads) cbuf[i] = b[s + 4 + i];
+      for (uint32_t i = lane; i < w.size; i += kFindThreads) cbuf[i] = b[w.data + i];
       __syncthreads();
-      uint32_t t = 0, v = 0;
-      for (int shift = 0;; shift += 7) {  // varint decoded length (validated by the size pass)
-        const uint32_t c = cbuf[t++];
-        v |= (c & 0x7f) << shift;
-        if (c < 0x80) break;
-      }
-      ulen = v;
-      uint32_t d = 0;
-      while (t < bl) {
-        const uint32_t tag = cbuf[t];
-        uint32_t len, off = 0;
-        if ((tag & 3) == 0) {  // literal
-          uint32_t x = tag >> 2;
-          if (x < 60) {
-            t += 1;
-          } else {
-            const uint32_t nb = x - 59;
-            if (t + 1 + nb > bl) { status = TSG_E_CORRUPT; break; }
-            x = 0;
-            for (uint32_t q = 0; q < nb; q++) x |= uint32_t(cbuf[t + 1 + q]) << (8 * q);
-            t += 1 + nb;
-          }
-          len = x + 1;
-          if (len == 0 || len > bl - t || len > ulen - d) { status = TSG_E_CORRUPT; break; }
-          for (uint32_t j = lane; j < len; j += kFindThreads) obuf[d + j] = cbuf[t + j];
-          t += len;
-          d += len;
-          continue;
-        }
-        if ((tag & 3) == 1) {
-          if (t + 2 > bl) { status = TSG_E_CORRUPT; break; }
-          len = 4 + ((tag >> 2) & 7);
-          off = ((tag & 0xe0) << 3) | cbuf[t + 1];
-          t += 2;
-        } else if ((tag & 3) == 2) {
-          if (t + 3 > bl) { status = TSG_E_CORRUPT; break; }
-          len = 1 + (tag >> 2);
-          off = uint32_t(cbuf[t + 1]) | uint32_t(cbuf[t + 2]) << 8;
-          t += 3;
-        } else {
-          if (t + 5 > bl) { status = TSG_E_CORRUPT; break; }
-          len = 1 + (tag >> 2);
-          off = uint32_t(cbuf[t + 1]) | uint32_t(cbuf[t + 2]) << 8 | uint32_t(cbuf[t + 3]) << 16 |
-                uint32_t(cbuf[t + 4]) << 24;
-          t += 5;
-        }
-        if (off == 0 || off > d || len > ulen - d) { status = TSG_E_CORRUPT; break; }
-        // LZ77 copy: out[d + j] = out[d - off + j % off] (periodic when off < len)
-        if (off >= len) {
-          for (uint32_t j = lane; j < len; j += kFindThreads) obuf[d + j] = obuf[d - off + j];
-        } else {
-          for (uint32_t j = lane; j < len; j += kFindThreads) obuf[d + j] = obuf[d - off + j % off];
-        }
-        d += len;
-      }
-      if (status == TSG_OK && d != ulen) status = TSG_E_CORRUPT;
+      status = snap_block_wave(cbuf, w.block - w.data, w.size, obuf, ulen, lane);
     }
     __syncthreads();
     if (status != TSG_OK) break;
-    // CRC-32C of the decoded chunk: 1 KiB per lane, combined on lane 0
-    {
-      uint32_t r = 0;  // raw register from state 0
-      const uint32_t lo = uint32_t(lane) * 1024, hi = min(ulen, lo + 1024);
-      for (uint32_t i = lo; i < hi; i++) r = tab[(r ^ obuf[i]) & 0xff] ^ (r >> 8);
-      lane_crc[lane] = r;
-      __syncthreads();
-      if (lane == 0) {
-        uint32_t acc = 0xffffffffu;
-        const uint32_t nseg = (ulen + 1023) / 1024;
-        for (uint32_t g = 0; g < nseg; g++) {
-          const uint32_t sl = min(ulen - g * 1024, 1024u);
-          uint32_t z = 0;
-          if (sl == 1024) {  // advance by 1024 zero bytes: linear map, precomputed columns
-            for (int bb = 0; bb < 32; bb++)
-              if ((acc >> bb) & 1u) z ^= crc->z1024[bb];
-          } else {
-            z = acc;
-            for (uint32_t i = 0; i < sl; i++) z = tab[z & 0xff] ^ (z >> 8);
-          }
-          acc = z ^ lane_crc[g];
-        }
-        const uint32_t c = ~acc;
-        const uint32_t masked = ((c >> 15) | (c << 17)) + 0xa282ead8u;  // snappy.go:61-64
-        lane_crc[0] = masked == want ? 1u : 0u;
-      }
-      __syncthreads();
-      if (!lane_crc[0]) status = TSG_E_CORRUPT;
-      __syncthreads();
-    }
-    if (status != TSG_OK) break;
-    if (pos + ulen > P.out_len) { status = TSG_E_CORRUPT; break; }
+    if (snapdev::crc_mask(wave_crc32c(obuf, ulen, tab, lane_crc, crc, lane)) != w.crc) status = TSG_E_CORRUPT;
+    if (status != TSG_OK || pos + ulen > P.out_len) { status = TSG_E_CORRUPT; break; }
     for (uint32_t i = lane; i < ulen; i += kFindThreads) out[pos + i] = obuf[i];
     pos += ulen;
-    s += cl;
     __syncthreads();
   }
   if (lane == 0 && (status != TSG_OK || pos != P.out_len)) P.status = status != TSG_OK ? status : TSG_E_CORRUPT;
@@ -299,9 +231,10 @@ extern "C" __global__ void __launch_bounds__(kFindThreads) find_decode_kernel(Fi
 extern "C" __global__ void __launch_bounds__(64) find_decode_zstd_kernel(FindPage *pages, uint8_t *arena) {
   __shared__ zdev::Work W;
   FindPage &P = pages[blockIdx.x];
-  if (P.status != TSG_OK || P.enc != 7 || threadIdx.x != 0) return;
+  if (P.status != TSG_OK || P.codec() != PageCodec::Zstd || threadIdx.x != 0) return;
   uint64_t len = 0;
-  const int st = zdev::zstd_decode(P.src + 6, P.len - 6, arena + P.out_off, P.out_len, len, W);
+  const auto [b, n, out] = page_io(P, arena);
+  const int st = zdev::zstd_decode(b, n, out, P.out_len, len, W);
   if (st != TSG_OK) P.status = st;
   else P.out_len = uint32_t(len);  // (the size pass may hold an upper bound)
 }
@@ -319,9 +252,10 @@ extern "C" __global__ void __launch_bounds__(kFindThreads) find_decode_zstd_wave
   __shared__ zdev::Work W;
   __shared__ zdev::WaveWork X;
   FindPage &P = pages[blockIdx.x];
-  if (P.status != TSG_OK || P.enc != 7) return;
+  if (P.status != TSG_OK || P.codec() != PageCodec::Zstd) return;
   uint64_t len = 0;
-  const int st = zdev::zstd_decode_wave(P.src + 6, P.len - 6, arena + P.out_off, P.out_len, len, W, X, threadIdx.x);
+  const auto [b, n, out] = page_io(P, arena);
+  const int st = zdev::zstd_decode_wave(b, n, out, P.out_len, len, W, X, threadIdx.x);
   if (threadIdx.x != 0) return;
   if (st != TSG_OK) P.status = st;
   else P.out_len = uint32_t(len);  // (the size pass may hold an upper bound)
@@ -349,7 +283,7 @@ __device__ uint32_t lz_wave_xxh32(const uint8_t *p, uint64_t n, int lane) {
   uint32_t v = lane == 0 ? lz4dev::kP1 + lz4dev::kP2 : lane == 1 ? lz4dev::kP2 : lane == 2 ? 0u : 0u - lz4dev::kP1;
   const uint64_t ns = n / 16;
   if (lane < 4)
-    for (uint64_t i = 0; i < ns; i++) v = lz4dev::xxh_round(v, lz4dev::rd32(p + 16 * i + 4 * lane));
+    for (uint64_t i = 0; i < ns; i++) v = lz4dev::xxh_round(v, rd32(p + 16 * i + 4 * lane));
   const uint32_t v0 = __shfl(v, 0, 64), v1 = __shfl(v, 1, 64), v2 = __shfl(v, 2, 64), v3 = __shfl(v, 3, 64);
   return lz4dev::xxh_finish(n >= 16 ? lz4dev::xxh_merge(v0, v1, v2, v3) : lz4dev::kP5, p + 16 * ns, n);
 }
@@ -446,10 +380,8 @@ extern "C" __global__ void __launch_bounds__(kFindThreads) find_decode_lz4_kerne
   __shared__ uint8_t ibuf[kLzIn];
   const int lane = threadIdx.x;
   FindPage &P = pages[blockIdx.x];
-  if (P.status != TSG_OK || P.enc < 2 || P.enc > 5) return;
-  const uint8_t *b = P.src + 6;
-  const uint32_t n = P.len - 6;
-  uint8_t *out = arena + P.out_off;
+  if (P.status != TSG_OK || P.codec() != PageCodec::Lz4) return;
+  const auto [b, n, out] = page_io(P, arena);
   lz4dev::Frame f;
   int32_t status = lz4dev::lz4_header(b, n, f);  // (accepted by the size pass already)
   if (status == TSG_OK && !(f.flags & lz4dev::kFlagIndep)) status = TSG_E_UNSUPPORTED;
@@ -484,7 +416,7 @@ extern "C" __global__ void __launch_bounds__(kFindThreads) find_decode_lz4_kerne
   }
   if (status == TSG_OK && (f.flags & lz4dev::kFlagContentSum)) {
     __syncthreads();
-    if (n - w.s < 4 || lz4dev::rd32(b + w.s) != lz_wave_xxh32(out, pos, lane)) status = TSG_E_CORRUPT;
+    if (n - w.s < 4 || rd32(b + w.s) != lz_wave_xxh32(out, pos, lane)) status = TSG_E_CORRUPT;
   }
   if (status == TSG_OK && pos != P.out_len) status = TSG_E_CORRUPT;
   if (lane == 0 && status != TSG_OK) P.status = status;
@@ -501,9 +433,6 @@ struct FindHitOut {
   uint32_t len;
   int32_t status;  // TSG_OK found, TSG_E_NOT_FOUND none (findOne returns nil), else the page error
 };
-__device__ __forceinline__ uint32_t lds_le32(const uint8_t *p) {
-  return uint32_t(p[0]) | uint32_t(p[1]) << 8 | uint32_t(p[2]) << 16 | uint32_t(p[3]) << 24;
-}
 constexpr int kFindPer = 4;  // pending ids held in registers per lane and pass
 extern "C" __global__ void __launch_bounds__(kFindThreads) find_scan_kernel(const FindPage *pages, const uint8_t *arena,
                                                                           const uint8_t *hit_ids, FindHitOut *res) {
@@ -524,7 +453,7 @@ extern "C" __global__ void __launch_bounds__(kFindThreads) find_scan_kernel(cons
       const uint32_t h = base + uint32_t(k) * kFindThreads + lane;
       pend[k] = h < P.nhit;
 #pragma unroll
-      for (int q = 0; q < 4; q++) id[k][q] = pend[k] ? g_le32(hit_ids + uint64_t(P.hit0 + h) * 16 + 4 * q) : 0u;
+      for (int q = 0; q < 4; q++) id[k][q] = pend[k] ? rd32(hit_ids + uint64_t(P.hit0 + h) * 16 + 4 * q) : 0u;
       mine += pend[k] ? 1u : 0u;
     }
     uint32_t remaining = mine;
@@ -549,7 +478,7 @@ extern "C" __global__ void __launch_bounds__(kFindThreads) find_scan_kernel(cons
           break;
         }
         if (wl - w < 8) break;  // (the window ends before the page does) slide
-        const uint32_t total = lds_le32(win + w), il = lds_le32(win + w + 4);
+        const uint32_t total = rd32(win + w), il = rd32(win + w + 4);
         if (R == 8) {  // reading the object bytes at EOF: io.EOF
           end = true;
           break;
@@ -562,7 +491,7 @@ extern "C" __global__ void __launch_bounds__(kFindThreads) find_scan_kernel(cons
           if (wl - w < 24) break;  // slide
           uint32_t oid[4];
 #pragma unroll
-          for (int q = 0; q < 4; q++) oid[q] = lds_le32(win + w + 8 + 4 * q);
+          for (int q = 0; q < 4; q++) oid[q] = rd32(win + w + 8 + 4 * q);
           bool got = false;
 #pragma unroll
           for (int k = 0; k < kFindPer; k++)
@@ -696,9 +625,10 @@ void device_find(DeviceCtx &dc, const std::vector<std::pair<uint32_t, V2Block *>
   find_decode_kernel<<<np, kFindThreads, 0, s>>>(static_cast<FindPage *>(dpages.p), static_cast<uint8_t *>(darena.p),
                                                static_cast<const CrcArgs *>(dc.fcrc.p));
   HIP_OK(hipGetLastError());
-  bool any_zstd = false;
-  for (auto &pg : pages) any_zstd = any_zstd || (pg.enc == 7 && pg.status == TSG_OK);
-  if (any_zstd) {
+  auto any = [&](PageCodec c) {  // a page of that codec the size pass accepted
+    return std::any_of(pages.begin(), pages.end(), [c](const FindPage &pg) { return pg.status == TSG_OK && pg.codec() == c; });
+  };
+  if (any(PageCodec::Zstd)) {
     if (g_zstd_lane.load(std::memory_order_relaxed))
       find_decode_zstd_kernel<<<np, 64, 0, s>>>(static_cast<FindPage *>(dpages.p), static_cast<uint8_t *>(darena.p));
     else
@@ -706,9 +636,7 @@ void device_find(DeviceCtx &dc, const std::vector<std::pair<uint32_t, V2Block *>
                                                                static_cast<uint8_t *>(darena.p));
     HIP_OK(hipGetLastError());
   }
-  bool any_lz4 = false;
-  for (auto &pg : pages) any_lz4 = any_lz4 || (pg.enc >= 2 && pg.enc <= 5 && pg.status == TSG_OK);
-  if (any_lz4) {
+  if (any(PageCodec::Lz4)) {
     find_decode_lz4_kernel<<<np, kFindThreads, 0, s>>>(static_cast<FindPage *>(dpages.p),
                                                        static_cast<uint8_t *>(darena.p));
     HIP_OK(hipGetLastError());

@@ -142,11 +142,7 @@ static size_t put_data_page(std::vector<uint8_t> &file, const uint8_t *payload, 
 // CutPage: compress the object buffer, page = [u32 total][u16 0][payload] (page.go:110-146)
 static size_t cut_data_page(std::vector<uint8_t> &file, const std::vector<uint8_t> &objects, int enc) {
   std::vector<uint8_t> payload;
-  if (enc == 6) snappy_framed_encode(objects.data(), objects.size(), payload);
-  else if (enc == 0) payload = objects;
-  else if (is_lz4_encoding(enc)) lz4_frame_encode(objects.data(), objects.size(), enc, payload);
-  else if (enc == 7) zstd_frame_encode(objects.data(), objects.size(), payload);
-  else fail(TSG_E_UNSUPPORTED_ENCODING, std::string("writer: unsupported encoding ") + encoding_name(enc));
+  page_encode(enc, objects, payload);
   return put_data_page(file, payload.data(), payload.size());
 }
 
@@ -255,8 +251,7 @@ struct SearchBlockWriter::Impl {
 };
 
 SearchBlockWriter::SearchBlockWriter(const std::string &dir, int enc, uint32_t page_size) : p_(new Impl) {
-  if (enc != 0 && enc != 6 && enc != 7 && !is_lz4_encoding(enc))
-    fail(TSG_E_UNSUPPORTED_ENCODING, "writer supports none/snappy/lz4/zstd");
+  require_page_encoding(enc, "writer supports none/snappy/lz4/zstd");
   p_->dir = dir;
   p_->enc = enc;
   p_->page_size = page_size ? page_size : 2 * 1024 * 1024;  // defaultBackendSearchBlockPageSize

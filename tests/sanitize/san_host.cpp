@@ -7,7 +7,8 @@
 //    decode either succeeds or throws a tsg error — never an out-of-bounds access.
 // 2. The v2 trace blocks the reference ships (tests/golden/v2test: snappy, tests/golden/tempo_cli:
 //    zstd): index pages (xxhash64 checksums) and data pages decoded, then fuzzed the same way.
-// 3. snappy framing round trips, and the host zstd decoder on corrupted frames.
+// 3. snappy framing round trips and a fixed list of framing damages (each rejected), and the host
+//    zstd decoder on corrupted frames.
 // Usage: san_host <tmpdir> <golden dir> <fuzz iterations>
 #include <sys/stat.h>
 
@@ -165,6 +166,49 @@ int main(int argc, char **argv) {
       snappy_framed_decode(enc.data(), enc.size(), dec);
     } catch (const Error &) {
     }
+  }
+  {  // the framing damages of tests/snappy_frames.py on one of the encoder's frames: each is rejected
+    std::vector<uint8_t> src(3000), enc, dec;
+    for (size_t i = 0; i < src.size(); i++) src[i] = uint8_t(i % 97);
+    snappy_framed_encode(src.data(), src.size(), enc);
+    // enc: [ff 06 00 00 "sNaPpY"] [00 len24] [crc32] [varint 3000: b8 17] [block]
+    CHECK(enc.size() > 20 && enc[10] == 0x00 && enc[18] == 0xb8 && enc[19] == 0x17);
+    auto rejected = [&dec](const std::vector<uint8_t> &f) {
+      try {
+        snappy_framed_decode(f.data(), f.size(), dec);
+      } catch (const Error &e) {
+        return e.code == TSG_E_CORRUPT;
+      }
+      return false;
+    };
+    auto with_varint = [&enc](std::initializer_list<uint8_t> v) {  // the decoded length respelled
+      std::vector<uint8_t> f = enc;
+      f.erase(f.begin() + 18, f.begin() + 20);
+      f.insert(f.begin() + 18, v);
+      const uint32_t cl = (uint32_t(f[11]) | uint32_t(f[12]) << 8) + uint32_t(v.size()) - 2;  // the chunk's length
+      f[11] = uint8_t(cl);
+      f[12] = uint8_t(cl >> 8);
+      return f;
+    };
+    CHECK(!rejected(enc) && dec == src);
+    CHECK(!rejected(with_varint({0xb8, 0x97, 0x80, 0x80, 0x80, 0x00})) && dec == src);  // padded to 6 bytes
+    CHECK(!rejected(with_varint({0xb8, 0x97, 0x80, 0x80, 0x80, 0x80, 0x80, 0x80, 0x80, 0x00})) && dec == src);
+    std::vector<std::vector<uint8_t>> bad;
+    auto damage = [&](auto &&edit) {
+      bad.push_back(enc);
+      edit(bad.back());
+    };
+    damage([](auto &f) { f[14] ^= 1; });                                               // flipped checksum
+    damage([](auto &f) { f[12] += 1; });                                               // chunk length past the page
+    damage([](auto &f) { f.insert(f.end(), {0xfe, 0x00, 0x00}); });                    // partial chunk header
+    damage([](auto &f) { f.erase(f.begin(), f.begin() + 10); });                       // no stream identifier first
+    damage([](auto &f) { f[9] = 'y'; });                                               // wrong identifier bytes
+    damage([](auto &f) { f.insert(f.begin() + 10, {0x02, 0x02, 0x00, 0x00, 'x', 'x'}); });       // reserved unskippable
+    damage([](auto &f) { f.insert(f.begin() + 10, {0x01, 0x03, 0x00, 0x00, 'a', 'b', 'c'}); });  // uncompressed, cl < 4
+    bad.push_back(with_varint({0xb8, 0x97, 0x80, 0x80, 0x80, 0x80, 0x80, 0x80, 0x80, 0x02}));    // Uvarint overflow
+    bad.push_back(with_varint({0x81, 0x80, 0x04}));                                    // decoded length 65 537
+    for (const auto &f : bad) CHECK(rejected(f));
+    std::printf("snappy framing: %zu damages rejected\n", bad.size());
   }
   {
     const std::vector<uint8_t> index = slurp(golden + "/tempo_cli/index"), data = slurp(golden + "/tempo_cli/data");
