@@ -267,6 +267,36 @@ int tsg_wal_block_open(tsg_ctx *ctx, const char *path, int device_hint, tsg_bloc
 int tsg_wal_block_open_mem(tsg_ctx *ctx, const uint8_t *data, size_t len, int encoding, int device_hint,
                            tsg_block **out);
 
+/* The ingester's head block: the WAL file of an open WAL block has grown (StreamingSearchBlock
+ * is appended to while it is searched, streaming_search_block.go:118-237). *out becomes a new
+ * handle on old's device, equal in every observable respect (info, tags, tag values, search
+ * results and metrics) to tsg_wal_block_open of the file as it is now. Only the appended bytes
+ * are parsed; the new block's columns are written on the device from old's columns and the few
+ * new or changed entries. old is not modified and stays searchable until its own
+ * tsg_block_close, before or after the new handle's (searches in flight on it are not
+ * disturbed). stats may be NULL.
+ *   mode 1  incremental: bytes_replayed is exactly the length of the good pages appended.
+ *   mode 0  nothing new (also: old is partial and its damaged page is still damaged): *out is a
+ *           clone of old (tsg_block_clone's cost) sharing its host side.
+ *   mode 2  full reopen, the reason in tsg_last_error: the file is shorter than what old was
+ *           replayed from, or the last page old replayed is no longer there byte for byte (a
+ *           file rotated under the same name).
+ * A handle that is not a WAL block -> TSG_E_UNSUPPORTED. A damaged appended page ends the
+ * replay as at open (the pages before it are kept, tsg_block_info.partial = 1). */
+typedef struct tsg_wal_refresh_stats {
+  uint64_t bytes_replayed;    /* file bytes parsed by this call (the appended tail only, mode 1) */
+  uint64_t pages_replayed;
+  uint64_t entries_added;     /* new ids */
+  uint64_t entries_combined;  /* appended pages whose id already had an entry (DataCombiner) */
+  uint64_t upload_bytes;      /* host->device bytes of this call */
+  uint64_t kernel_ns;
+  int32_t  mode;              /* 1 incremental, 2 full reopen (fallback, reason in tsg_last_error), 0 nothing new */
+} tsg_wal_refresh_stats;
+int tsg_wal_block_refresh(tsg_ctx *ctx, const tsg_block *old, const char *path, tsg_block **out,
+                          tsg_wal_refresh_stats *stats);
+int tsg_wal_block_refresh_mem(tsg_ctx *ctx, const tsg_block *old, const uint8_t *data, size_t len, tsg_block **out,
+                              tsg_wal_refresh_stats *stats);
+
 /* ---- live traces (instance.searchLiveTraces) -------------------------------------- */
 /* A snapshot of the ingester's live traces (i.traces, in its iteration order), copied in:
  * segment i = bytes[seg_off[i], seg_off[i+1]) is one searchData buffer as the distributor

@@ -257,10 +257,6 @@ void parse_entry(const FbTable &e, const uint8_t *fb, uint32_t fb_base, PagePars
   pp.tag_begin.push_back(uint32_t(pp.tag_kv.size()));
 }
 
-struct KeyBuild {
-  std::unordered_map<std::string, uint32_t> vmap;
-  std::unordered_map<std::string, uint32_t> smap;
-};
 }  // namespace
 
 
@@ -368,7 +364,12 @@ static void merge_page(HostBlock &hb, std::vector<KeyBuild> &kb, PageParse &pp) 
 // engine interns once per context and matches once per query on the host (the one-launch
 // search path takes the resulting 256-bit set bitmaps in its kernel arguments).
 // Ids are internal; scan order, set membership and Value(0) are unchanged.
-static void canonicalize_narrow_keys(HostBlock &hb) {
+// vmaps / smaps (optional, one vector per key): old value / set id -> new id of the keys
+// renumbered here, empty for the others.
+static void canonicalize_narrow_keys(HostBlock &hb, std::vector<std::vector<uint32_t>> *vmaps = nullptr,
+                                     std::vector<std::vector<uint32_t>> *smaps = nullptr) {
+  if (vmaps) vmaps->assign(hb.keys.size(), {});
+  if (smaps) smaps->assign(hb.keys.size(), {});
   for (size_t k = 0; k < hb.keys.size(); k++) {
     KeyColumn &kc = hb.keys[k];
     if (kc.width() != 1) continue;
@@ -412,6 +413,8 @@ static void canonicalize_narrow_keys(HostBlock &hb) {
     if (int(k) == hb.name_key)
       for (auto &v : hb.name_vid)
         if (v != kNone) v = vnew[v];
+    if (vmaps) (*vmaps)[k] = std::move(vnew);
+    if (smaps) (*smaps)[k] = std::move(snew);
   }
 }
 
@@ -1482,22 +1485,19 @@ void header_add_entry(HostBlock &hb, const uint8_t *obj, size_t n) {
 }
 }  // namespace
 
-void decode_wal_search_block(const uint8_t *file, size_t len, int enc, HostBlock &hb) {
-  hb = HostBlock();
-  hb.has_meta = true;
-  hb.streaming = true;
-  hb.meta.version = "v2";
-  hb.meta.encoding = enc;
-  require_page_encoding(enc, std::string("search encoding not supported: ") + encoding_name(enc));
-  struct Rec {
-    std::string id;
-    std::vector<uint8_t> obj;
-  };
-  std::vector<Rec> recs;
-  // ReplayWALAndGetRecords: pages in file order until EOF; a damaged page ends the
-  // replay with a warning and keeps the records before it
+namespace {
+struct WalRec {
+  std::string id;
+  std::vector<uint8_t> obj;
+};
+
+// ReplayWALAndGetRecords over file[off, len): pages in file order until EOF; a damaged page
+// ends the replay with a warning (hb.partial) and keeps the records before it. Returns the
+// offset behind the last good page; last_off = where that page starts.
+uint64_t replay_wal_pages(const uint8_t *file, size_t len, uint64_t off, int enc, HostBlock &hb,
+                          std::vector<WalRec> &recs, uint64_t &last_off) {
   std::vector<uint8_t> buf;
-  for (size_t off = 0; off < len;) {
+  while (off < len) {
     try {
       if (len - off < 6) fail(TSG_E_CORRUPT, "truncated page header");
       const uint32_t total = le32(file + off);
@@ -1511,45 +1511,287 @@ void decode_wal_search_block(const uint8_t *file, size_t len, int enc, HostBlock
       const uint32_t ot = le32(buf.data()), il = le32(buf.data() + 4);
       if (ot < 8 || ot - 8 > buf.size() - 8 || il > ot - 8) fail(TSG_E_CORRUPT, "object out of bounds");
       if (buf.size() != ot) fail(TSG_E_CORRUPT, "expected EOF after the page's object");
-      Rec r;
+      WalRec r;
       r.id.assign(reinterpret_cast<const char *>(buf.data() + 8), il);
       r.obj.assign(buf.data() + 8 + il, buf.data() + ot);
       header_add_entry(hb, r.obj.data(), r.obj.size());  // handleObj
       recs.push_back(std::move(r));
+      last_off = off;
       off += total;
     } catch (const Error &) {
       hb.partial = true;
       break;
     }
   }
-  if (recs.empty()) fail(TSG_E_NOT_FOUND, "empty wal file");  // RescanBlocks drops it
-  // common.SortRecords (bytes order of ids; equal ids combine order-independently)
-  std::stable_sort(recs.begin(), recs.end(), [](const Rec &a, const Rec &b) { return a.id < b.id; });
-  std::vector<KeyBuild> kb;
+  return off;
+}
+
+// One entry of the deduping iterator (its object: a page's, or DataCombiner's) appended to hb.
+void add_wal_entry(HostBlock &hb, std::vector<KeyBuild> &kb, std::vector<uint8_t> obj,
+                   std::vector<std::shared_ptr<const std::vector<uint8_t>>> &objs) {
   PageParse pp;
+  pp.buf = std::move(obj);
+  pp.fb_bytes = pp.buf.size();  // sr.AddBytesInspected(len(obj))
+  pp.nentries = 1;
+  pp.tag_begin.push_back(0);
+  FbTable e = FbTable::root(pp.buf.data(), pp.buf.size());
+  std::unordered_map<uint32_t, uint32_t> memo;
+  parse_entry(e, pp.buf.data(), 0, pp, memo);
+  merge_page(hb, kb, pp);
+  objs.push_back(std::make_shared<const std::vector<uint8_t>>(std::move(pp.buf)));
+}
+
+KeyColumn dict_only(const KeyColumn &kc) {
+  KeyColumn o;
+  o.name = kc.name;
+  o.dict_bytes = kc.dict_bytes;
+  o.dict_off = kc.dict_off;
+  o.set_off = kc.set_off;
+  o.set_vals = kc.set_vals;
+  o.identity = kc.identity;
+  return o;
+}
+
+// out = o with the plan's delta entries spliced in (w elements per entry)
+template <class V>
+void splice_entries(const WalRefreshPlan &p, const V &o, const V &dl, size_t w, V &out) {
+  out.clear();
+  out.reserve(size_t(p.n_new) * w);
+  size_t at = 0;
+  for (size_t d = 0; d < p.ndelta(); d++) {
+    out.insert(out.end(), o.begin() + long(at * w), o.begin() + long(size_t(p.dlo[d]) * w));
+    out.insert(out.end(), dl.begin() + long(d * w), dl.begin() + long((d + 1) * w));
+    at = size_t(p.dlo[d]) + (p.drep[d] ? 1 : 0);
+  }
+  out.insert(out.end(), o.begin() + long(at * w), o.begin() + long(size_t(p.n_old) * w));
+}
+}  // namespace
+
+void trim_uploaded_host(HostBlock &hb) {
+  for (size_t k = 0; k < hb.keys.size(); k++) {
+    auto &kc = hb.keys[k];
+    std::vector<uint32_t>().swap(kc.col);
+    if (int(k) != hb.svc_key && int(k) != hb.name_key) {
+      Bytes().swap(kc.dict_bytes);
+      std::vector<uint32_t>().swap(kc.dict_off);
+      std::vector<uint32_t>().swap(kc.set_vals);
+      kc.set_off.resize(1);
+    }
+  }
+}
+
+void decode_wal_search_block(const uint8_t *file, size_t len, int enc, HostBlock &hb) {
+  hb = HostBlock();
+  hb.has_meta = true;
+  hb.streaming = true;
+  hb.meta.version = "v2";
+  hb.meta.encoding = enc;
+  require_page_encoding(enc, std::string("search encoding not supported: ") + encoding_name(enc));
+  std::vector<WalRec> recs;
+  auto ws = std::make_shared<WalState>();
+  ws->consumed = replay_wal_pages(file, len, 0, enc, hb, recs, ws->last_off);
+  if (recs.empty()) fail(TSG_E_NOT_FOUND, "empty wal file");  // RescanBlocks drops it
+  ws->last_hash = xxhash64(file + ws->last_off, ws->consumed - ws->last_off);
+  // common.SortRecords (bytes order of ids; equal ids combine order-independently)
+  std::stable_sort(recs.begin(), recs.end(), [](const WalRec &a, const WalRec &b) { return a.id < b.id; });
+  ws->rid_off.push_back(0);
   for (size_t i = 0; i < recs.size();) {
     size_t j = i + 1;
     while (j < recs.size() && recs[j].id == recs[i].id) j++;
-    pp = PageParse();
+    std::vector<uint8_t> obj;
     if (j - i == 1) {
-      pp.buf = std::move(recs[i].obj);
+      obj = std::move(recs[i].obj);
     } else {  // dedupingIterator -> DataCombiner.Combine -> SearchEntryMutable.ToBytes
       SearchEntryIn d;
       for (size_t k = i; k < j; k++)
         if (!recs[k].obj.empty()) combine_into(d, recs[k].obj);
-      pp.buf = fb_search_entry_bytes(d);
+      obj = fb_search_entry_bytes(d);
     }
-    pp.fb_bytes = pp.buf.size();  // sr.AddBytesInspected(len(obj))
-    pp.nentries = 1;
-    pp.tag_begin.push_back(0);
-    FbTable e = FbTable::root(pp.buf.data(), pp.buf.size());
-    std::unordered_map<uint32_t, uint32_t> memo;
-    parse_entry(e, pp.buf.data(), 0, pp, memo);
-    merge_page(hb, kb, pp);
+    add_wal_entry(hb, ws->kb, std::move(obj), ws->objs);
+    ws->rid.insert(ws->rid.end(), recs[i].id.begin(), recs[i].id.end());
+    ws->rid_off.push_back(uint32_t(ws->rid.size()));
     i = j;
   }
   for (auto &kc : hb.keys) kc.col.resize(hb.n, kNone);
-  canonicalize_narrow_keys(hb);
+  for (const auto &kc : hb.keys) ws->keys.push_back(dict_only(kc));
+  canonicalize_narrow_keys(hb, &ws->vcanon, &ws->scanon);
+  hb.wal = std::move(ws);
+}
+
+void plan_wal_refresh(const HostBlock &old, const uint8_t *file, uint64_t base, uint64_t len, HostBlock &nb,
+                      WalRefreshPlan &plan) {
+  plan = WalRefreshPlan();
+  if (!old.streaming || !old.wal) fail(TSG_E_UNSUPPORTED, "not a WAL block: only tsg_wal_block_open's handles are refreshed");
+  const WalState &ws = *old.wal;
+  plan.n_old = plan.n_new = old.n;
+  // the same file, grown: the bytes this block was replayed from are still its prefix (their
+  // length, and the last page among them by hash: a file rotated under the same name fails it)
+  if (len < ws.consumed) {
+    plan.mode = 2;
+    plan.reason = "wal refresh: the file is shorter than the bytes already replayed; reopened";
+    return;
+  }
+  if (base > ws.last_off) fail(TSG_E_INVALID, "wal refresh: the bytes given start behind the block's last page");
+  if (xxhash64(file + (ws.last_off - base), ws.consumed - ws.last_off) != ws.last_hash) {
+    plan.mode = 2;
+    plan.reason = "wal refresh: the bytes already replayed have changed; reopened";
+    return;
+  }
+  nb = HostBlock();
+  nb.has_meta = true;
+  nb.streaming = true;
+  nb.meta = old.meta;
+  nb.stream_tags = old.stream_tags;  // the mutable header goes on from the old block's
+  nb.min_dur = old.min_dur;
+  nb.max_dur = old.max_dur;
+  std::vector<WalRec> recs;
+  auto nws = std::make_shared<WalState>();
+  nws->last_off = ws.last_off;
+  nws->last_hash = ws.last_hash;
+  // (a partial block's damaged page is parsed again: a page that was torn and has been
+  // completed since is replayed now, as a fresh open would; one still damaged ends the tail at once)
+  const uint8_t *tail = file + (ws.consumed - base);
+  uint64_t tail_last = 0;
+  const uint64_t tail_end = replay_wal_pages(tail, size_t(len - ws.consumed), 0, old.meta.encoding, nb, recs, tail_last);
+  nws->consumed = ws.consumed + tail_end;
+  plan.bytes_replayed = tail_end;
+  plan.pages_replayed = recs.size();
+  if (recs.empty() && nb.partial == old.partial) {
+    plan.mode = 0;
+    return;
+  }
+  plan.mode = 1;
+  if (!recs.empty()) {
+    nws->last_off = ws.consumed + tail_last;
+    nws->last_hash = xxhash64(tail + tail_last, tail_end - tail_last);
+  }
+  std::stable_sort(recs.begin(), recs.end(), [](const WalRec &a, const WalRec &b) { return a.id < b.id; });
+  // the delta entries, built like a block of their own over the old dictionaries
+  HostBlock dh;
+  for (const auto &kc : ws.keys) {
+    dh.key_index.emplace(kc.name, int(dh.keys.size()));
+    dh.keys.push_back(dict_only(kc));
+  }
+  dh.svc_key = old.svc_key;
+  dh.name_key = old.name_key;
+  std::vector<KeyBuild> kb = ws.kb;
+  std::vector<std::shared_ptr<const std::vector<uint8_t>>> dobjs;
+  Bytes drid;
+  std::vector<uint32_t> drid_off(1, 0);
+  uint64_t replaced_fb = 0;
+  uint32_t ins = 0;
+  for (size_t i = 0; i < recs.size();) {
+    size_t j = i + 1;
+    while (j < recs.size() && recs[j].id == recs[i].id) j++;
+    const std::string_view id = recs[i].id;
+    size_t lo = 0, hi = size_t(old.n);
+    while (lo < hi) {
+      const size_t m = (lo + hi) >> 1;
+      if (ws.record_id(m) < id) lo = m + 1;
+      else hi = m;
+    }
+    const bool found = lo < old.n && ws.record_id(lo) == id;
+    std::vector<uint8_t> obj;
+    if (!found && j - i == 1) {
+      obj = std::move(recs[i].obj);
+    } else {  // DataCombiner over the entry's object (itself a page's or an earlier combination) and the new pages'
+      SearchEntryIn d;
+      if (found && !ws.objs[lo]->empty()) combine_into(d, *ws.objs[lo]);
+      for (size_t k = i; k < j; k++)
+        if (!recs[k].obj.empty()) combine_into(d, recs[k].obj);
+      obj = fb_search_entry_bytes(d);
+    }
+    add_wal_entry(dh, kb, std::move(obj), dobjs);
+    drid.insert(drid.end(), id.begin(), id.end());
+    drid_off.push_back(uint32_t(drid.size()));
+    plan.dlo.push_back(uint32_t(lo));
+    plan.dins.push_back(ins);
+    plan.drep.push_back(found ? 1 : 0);
+    if (found) {
+      replaced_fb += old.page_fb_bytes[lo];
+    } else {
+      plan.entries_added++;
+      ins++;
+    }
+    i = j;
+  }
+  plan.dins.push_back(ins);
+  plan.entries_combined = plan.pages_replayed - plan.entries_added;  // (pages that met an entry with their id)
+  plan.n_new = old.n + ins;
+  if (plan.n_new >= 0xffffffffull) fail(TSG_E_UNSUPPORTED, "wal refresh: too many entries");
+  for (auto &kc : dh.keys) kc.col.resize(dh.n, kNone);
+  for (const auto &kc : dh.keys) nws->keys.push_back(dict_only(kc));
+  nws->kb = std::move(kb);
+  canonicalize_narrow_keys(dh, &nws->vcanon, &nws->scanon);
+  // old column ids -> new column ids, per key of the old block
+  auto lut_of = [](const std::vector<uint32_t> &oc, const std::vector<uint32_t> &nc, uint32_t n, std::vector<uint32_t> &lut) {
+    lut.clear();
+    if (oc.empty() && nc.empty()) return;
+    lut.resize(n);
+    for (uint32_t p = 0; p < n; p++) lut[oc.empty() ? p : oc[p]] = nc.empty() ? p : nc[p];
+  };
+  plan.set_lut.resize(ws.keys.size());
+  for (size_t k = 0; k < ws.keys.size(); k++) lut_of(ws.scanon[k], nws->scanon[k], ws.keys[k].nsets(), plan.set_lut[k]);
+  if (old.svc_key >= 0)
+    lut_of(ws.vcanon[size_t(old.svc_key)], nws->vcanon[size_t(old.svc_key)], ws.keys[size_t(old.svc_key)].nvals(), plan.svc_lut);
+  if (old.name_key >= 0)
+    lut_of(ws.vcanon[size_t(old.name_key)], nws->vcanon[size_t(old.name_key)], ws.keys[size_t(old.name_key)].nvals(), plan.name_lut);
+  // the delta's columns
+  plan.ids = std::move(dh.ids);
+  plan.id_len = std::move(dh.id_len);
+  plan.start = std::move(dh.start);
+  plan.end = std::move(dh.end);
+  plan.fb_bytes = std::move(dh.page_fb_bytes);
+  plan.svc_vid = std::move(dh.svc_vid);
+  plan.name_vid = std::move(dh.name_vid);
+  plan.dcol.resize(dh.keys.size());
+  for (size_t k = 0; k < dh.keys.size(); k++) plan.dcol[k] = std::move(dh.keys[k].col);
+  // the new block's host side
+  nb.n = plan.n_new;
+  nb.keys = std::move(dh.keys);
+  nb.key_index = std::move(dh.key_index);
+  nb.svc_key = dh.svc_key;
+  nb.name_key = dh.name_key;
+  splice_entries(plan, old.ids, plan.ids, 16, nb.ids);
+  splice_entries(plan, old.id_len, plan.id_len, 1, nb.id_len);
+  splice_entries(plan, old.start, plan.start, 1, nb.start);
+  splice_entries(plan, old.end, plan.end, 1, nb.end);
+  splice_entries(plan, old.page_fb_bytes, plan.fb_bytes, 1, nb.page_fb_bytes);
+  auto renumbered = [&](const std::vector<uint32_t> &v, const std::vector<uint32_t> &lut) {
+    std::vector<uint32_t> o(v.empty() ? std::vector<uint32_t>(size_t(old.n), kNone) : v);
+    if (!lut.empty())
+      for (auto &x : o)
+        if (x != kNone) x = lut[x];
+    return o;
+  };
+  splice_entries(plan, renumbered(old.svc_vid, plan.svc_lut), plan.svc_vid, 1, nb.svc_vid);
+  splice_entries(plan, renumbered(old.name_vid, plan.name_lut), plan.name_vid, 1, nb.name_vid);
+  nb.page_entries.assign(size_t(nb.n), 1);
+  nb.page_first.resize(size_t(nb.n));
+  for (size_t e = 0; e < nb.n; e++) nb.page_first[e] = e;
+  nb.fb_bytes = old.fb_bytes - replaced_fb;
+  for (uint64_t b : plan.fb_bytes) nb.fb_bytes += b;
+  splice_entries(plan, ws.objs, dobjs, 1, nws->objs);
+  // (record ids: variable length, spliced entry by entry)
+  nws->rid.reserve(ws.rid.size() + drid.size());
+  nws->rid_off.reserve(size_t(nb.n) + 1);
+  nws->rid_off.push_back(0);
+  {
+    size_t at = 0;
+    auto put = [&](const Bytes &src, const std::vector<uint32_t> &off, size_t e0, size_t e1) {
+      for (size_t e = e0; e < e1; e++) {
+        nws->rid.insert(nws->rid.end(), src.begin() + off[e], src.begin() + off[e + 1]);
+        nws->rid_off.push_back(uint32_t(nws->rid.size()));
+      }
+    };
+    for (size_t d = 0; d < plan.ndelta(); d++) {
+      put(ws.rid, ws.rid_off, at, plan.dlo[d]);
+      put(drid, drid_off, d, d + 1);
+      at = size_t(plan.dlo[d]) + (plan.drep[d] ? 1 : 0);
+    }
+    put(ws.rid, ws.rid_off, at, size_t(old.n));
+  }
+  nb.wal = std::move(nws);
 }
 
 void decode_live_block(const uint8_t *bytes, const uint64_t *seg_off, uint64_t nsegs, const uint64_t *trace_seg,

@@ -4,6 +4,7 @@
 #pragma once
 #include <cstdint>
 #include <map>
+#include <memory>
 #include <set>
 #include <string>
 #include <unordered_map>
@@ -129,12 +130,41 @@ struct KeyColumn {
   int width() const { return nsets() < 255 ? 1 : (nsets() < 65535 ? 2 : 4); }
 };
 
+// Interning tables of one key while a block is built: value bytes -> value id, the value ids of
+// a KeyValues table (4 bytes each) -> value set id
+struct KeyBuild {
+  std::unordered_map<std::string, uint32_t> vmap;
+  std::unordered_map<std::string, uint32_t> smap;
+};
+
+// What an open WAL block keeps so that the same file, grown, can be replayed from where this
+// replay ended (plan_wal_refresh): the bytes consumed and a hash of the last page among them,
+// the record ids in scan order, each entry's object (a later page with the same id is combined
+// into it), and the dictionaries as the replay numbered them (first seen), before the narrow
+// keys were renumbered (canonicalize_narrow_keys), with their interning tables.
+struct WalState {
+  uint64_t consumed = 0;   // file bytes replayed (the damaged page of a partial block not among them)
+  uint64_t last_off = 0;   // offset of the last replayed page
+  uint64_t last_hash = 0;  // xxhash64 of file[last_off, consumed)
+  Bytes rid;                      // record ids (object framing), scan order
+  std::vector<uint32_t> rid_off;  // n + 1
+  std::vector<std::shared_ptr<const std::vector<uint8_t>>> objs;  // per entry: its SearchEntry bytes
+  std::vector<KeyColumn> keys;  // dictionaries only (col empty), first-seen numbering
+  std::vector<KeyBuild> kb;
+  // per key: first-seen value / set id -> the id the block's columns hold (empty: the same)
+  std::vector<std::vector<uint32_t>> vcanon, scanon;
+  std::string_view record_id(size_t e) const {
+    return {reinterpret_cast<const char *>(rid.data()) + rid_off[e], rid_off[e + 1] - rid_off[e]};
+  }
+};
+
 struct HostBlock {
   bool has_meta = false;
   // WAL (StreamingSearchBlock) form: one entry per "page", no on-disk header; the
   // header is the SearchBlockHeaderMutable rebuilt during replay (exact-value Contains)
   bool streaming = false;
   bool partial = false;  // replay stopped at a damaged page (the reference's warning)
+  std::shared_ptr<const WalState> wal;  // WAL blocks: the replay state a refresh continues from
   // Backend blocks with damage: a failing index record ends the block silently (its
   // pages are not resident; index_truncated = true). A damaged data page k (read, page
   // framing, decompression, object framing, flatbuffer bounds) keeps pages [0, k)
@@ -217,6 +247,44 @@ void decode_search_block(const uint8_t *meta, size_t meta_len, bool meta_present
 // equal ids combined, each resulting entry one scan position whose bytesInspected
 // is its object length.
 void decode_wal_search_block(const uint8_t *file, size_t len, int enc, HostBlock &out);
+
+// ---- refresh of an open WAL block from the same file, grown -----------------------------
+// The host half: only file[consumed, len) is parsed. Its pages become delta entries, sorted by
+// id: a new id is an insert at its sorted position, an id the block already holds is combined
+// with that entry's object (DataCombiner) and replaces it. The delta's columns are numbered
+// against the block's dictionaries extended by the tail's new values and value sets; keys that
+// stay narrow are renumbered canonically, and the old columns reach the new numbering through
+// one table per key. The device half (devctx.hip block_refresh, wal_merge.hip) writes the new
+// block's columns from the old block's, the delta and those tables.
+struct WalRefreshPlan {
+  int mode = 0;        // 1 incremental, 2 reopen the whole file (reason), 0 nothing new
+  std::string reason;
+  uint64_t bytes_replayed = 0, pages_replayed = 0, entries_added = 0, entries_combined = 0;
+  uint64_t n_old = 0, n_new = 0;
+  // delta entries in id order. dlo[d]: old entries with a smaller id (a replace: the entry it
+  // replaces); dins[d]: inserts among the delta entries before d (ndelta + 1 values); the entry
+  // lands at scan position dlo[d] + dins[d] of the new block
+  std::vector<uint32_t> dlo, dins;
+  std::vector<uint8_t> drep;  // 1: replaces old entry dlo[d]
+  std::vector<uint8_t> ids, id_len;  // per delta entry, as HostBlock's
+  std::vector<uint64_t> start, end, fb_bytes;
+  std::vector<uint32_t> svc_vid, name_vid;     // new numbering
+  std::vector<std::vector<uint32_t>> dcol;     // per key of the new block: set id or kNone, new numbering
+  // per key of the old block: the set id its column holds -> the new block's (empty: unchanged)
+  std::vector<std::vector<uint32_t>> set_lut;
+  std::vector<uint32_t> svc_lut, name_lut;     // the same for the root names' value ids
+  size_t ndelta() const { return dlo.size(); }
+};
+// `nb` becomes the new block's host side (mode 1: keys hold the new dictionaries and no
+// columns, the per-entry record columns are merged already). Throws what a fresh
+// decode_wal_search_block of the file would throw for an appended page's object.
+// file = the file's bytes from offset `base` (at most the block's WalState::last_off: a caller
+// need not read what was replayed before) to its length `len`.
+void plan_wal_refresh(const HostBlock &old, const uint8_t *file, uint64_t base, uint64_t len, HostBlock &nb,
+                      WalRefreshPlan &plan);
+// What stays on the host once the device holds a block's columns (capi.cpp open_common).
+void trim_uploaded_host(HostBlock &hb);
+
 // Live traces: segment i = bytes[seg_off[i], seg_off[i+1]) (a SearchEntry flatbuffer as the
 // distributor wrote it), trace t = segments [trace_seg[t], trace_seg[t+1]). Every segment is
 // one row (its own Matches, pitfall P3 resolved per table as for WAL entries).

@@ -631,16 +631,60 @@ static void open_common(tsg_ctx *ctx, Decode &&decode, int device_hint, tsg_bloc
   // "positions -> records", fill_records_direct; kept as columns: at the densities where the
   // gather matters each column is read as a near-sequential stream, which 48-byte rows per
   // entry were not (twice the gather time in cfg4's statement+url query)
-  for (size_t k = 0; k < b->b.host->keys.size(); k++) {
-    auto &kc = b->b.host->keys[k];
-    std::vector<uint32_t>().swap(kc.col);
-    if (int(k) != b->b.host->svc_key && int(k) != b->b.host->name_key) {
-      Bytes().swap(kc.dict_bytes);
-      std::vector<uint32_t>().swap(kc.dict_off);
-      std::vector<uint32_t>().swap(kc.set_vals);
-      kc.set_off.resize(1);
+  trim_uploaded_host(*b->b.host);
+  *out = b;
+}
+
+// the position of a resident block's device in its context (a device_hint that lands on it)
+static int device_index(tsg_ctx *ctx, const tsg_block *b) {
+  for (size_t i = 0; i < ctx->c.devs.size(); i++)
+    if (ctx->c.devs[i] == b->b.dc) return int(i);
+  fail(TSG_E_INVALID, "the block is not resident on a device of this context");
+}
+
+// tsg_wal_block_refresh[_mem]: the file's bytes -> a handle equal to a fresh open of them
+// (data = the file from offset base on, len = the file's length; whole() gives all of it for the fallback)
+template <class Whole>
+static void wal_refresh_common(tsg_ctx *ctx, const tsg_block *old, const uint8_t *data, uint64_t base, uint64_t len,
+                               Whole &&whole, tsg_block **out, tsg_wal_refresh_stats *stats) {
+  using clk = std::chrono::steady_clock;
+  const auto t0 = clk::now();
+  tsg_wal_refresh_stats st{};
+  const HostBlock &oh = *old->b.host;
+  if (!oh.streaming || !oh.wal) fail(TSG_E_UNSUPPORTED, "tsg_wal_block_refresh: not a WAL block (tsg_wal_block_open's handles only)");
+  auto *b = new tsg_block();
+  b->ctx = ctx;
+  try {
+    WalRefreshPlan plan;
+    plan_wal_refresh(oh, data, base, len, *b->b.host, plan);
+    st.mode = plan.mode;
+    if (plan.mode == 0) {  // nothing new: a clone on the same device (host side shared)
+      block_clone(ctx->c, old->b, b->b, device_index(ctx, old));
+    } else if (plan.mode == 2) {  // not this block's file any more: a full open
+      set_last_error(plan.reason);
+      const uint8_t *all = whole();
+      decode_wal_search_block(all, size_t(len), oh.meta.encoding, *b->b.host);
+      block_upload(ctx->c, b->b, device_index(ctx, old));
+      trim_uploaded_host(*b->b.host);
+      st.bytes_replayed = b->b.host->wal->consumed;
+      st.pages_replayed = 0;  // (not counted by the full replay)
+      st.upload_bytes = b->b.dev.bytes;
+    } else {
+      if (!block_refresh) fail(TSG_E_DEVICE, "tsg_wal_block_refresh: this build of the library has no device half");
+      st.bytes_replayed = plan.bytes_replayed;
+      st.pages_replayed = plan.pages_replayed;
+      st.entries_added = plan.entries_added;
+      st.entries_combined = plan.entries_combined;
+      block_refresh(ctx->c, old->b, b->b, plan, st.upload_bytes, st.kernel_ns);
+      trim_uploaded_host(*b->b.host);
     }
+  } catch (...) {
+    block_free(b->b);
+    delete b;
+    throw;
   }
+  if (prof_on()) prof_add("wal.refresh", std::chrono::duration<double, std::micro>(clk::now() - t0).count());
+  if (stats) *stats = st;
   *out = b;
 }
 
@@ -838,6 +882,44 @@ int tsg_wal_block_open_mem(tsg_ctx *ctx, const uint8_t *data, size_t len, int en
   return guard([&] {
     open_common(ctx, [&](HostBlock &h) { decode_wal_search_block(data, len, encoding, h); }, device_hint, out);
   });
+}
+int tsg_wal_block_refresh(tsg_ctx *ctx, const tsg_block *old, const char *path, tsg_block **out,
+                          tsg_wal_refresh_stats *stats) {
+  if (!ctx || !old || !path || !out) return TSG_E_INVALID;
+  return guard([&] {
+    // only the block's last page and what follows it are read (a fallback reads the rest)
+    const int fd = ::open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) fail(TSG_E_IO, std::string("wal file missing: ") + std::strerror(errno));
+    struct Fd {
+      int fd;
+      ~Fd() { ::close(fd); }
+    } guard_fd{fd};
+    struct stat st;
+    if (fstat(fd, &st) != 0) fail(TSG_E_IO, std::string("fstat: ") + std::strerror(errno));
+    const uint64_t len = uint64_t(st.st_size);
+    auto read_at = [&](uint64_t from, std::vector<uint8_t> &buf) {
+      buf.resize(size_t(len - from));
+      for (size_t got = 0; got < buf.size();) {
+        const ssize_t r = ::pread(fd, buf.data() + got, buf.size() - got, off_t(from + got));
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) fail(TSG_E_IO, "wal file: short read");
+        got += size_t(r);
+      }
+    };
+    const WalState *ws = old->b.host->wal.get();
+    const uint64_t base = ws && ws->last_off <= len ? ws->last_off : len;
+    std::vector<uint8_t> tail, all;
+    read_at(base, tail);
+    wal_refresh_common(ctx, old, tail.data(), base, len, [&] {
+      read_at(0, all);
+      return static_cast<const uint8_t *>(all.data());
+    }, out, stats);
+  });
+}
+int tsg_wal_block_refresh_mem(tsg_ctx *ctx, const tsg_block *old, const uint8_t *data, size_t len, tsg_block **out,
+                              tsg_wal_refresh_stats *stats) {
+  if (!ctx || !old || (len && !data) || !out) return TSG_E_INVALID;
+  return guard([&] { wal_refresh_common(ctx, old, data, 0, len, [&] { return data; }, out, stats); });
 }
 int tsg_live_block_open_mem(tsg_ctx *ctx, const uint8_t *bytes, const uint64_t *seg_off, size_t nsegs,
                             const uint64_t *trace_seg, size_t ntraces, int device_hint, tsg_block **out) {

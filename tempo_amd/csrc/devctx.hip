@@ -13,6 +13,7 @@
 
 #include "aql.hpp"
 #include "devctx.hpp"
+#include "wal_merge.hpp"
 
 namespace tsg {
 
@@ -195,6 +196,72 @@ static std::shared_ptr<const NarrowDict> intern_narrow(Ctx &c, NarrowDict &&nd) 
   return p;
 }
 
+// One entry's scan columns: scan[0], scan[stride], scan[2 * stride], scan[3 * stride] = dur32,
+// start_s, end_s, ds (block_upload describes ds); dur64 = the exact duration.
+static inline void pack_scan(uint64_t start, uint64_t end, uint32_t *scan, size_t stride, uint64_t &dur64) {
+  const uint64_t dd = end - start;  // uint64 wrap (pitfall P2)
+  dur64 = dd;
+  scan[0] = dd >= 0xffffffffULL ? 0xffffffffu : uint32_t(dd);
+  const uint32_t ss = uint32_t(start / 1000000000ULL), es = uint32_t(end / 1000000000ULL);
+  scan[stride] = ss;
+  scan[2 * stride] = es;
+  const uint64_t q = dd / 1000000ULL;
+  const uint64_t d16 = q >= 0x8000ULL ? 0xffffULL : std::min<uint64_t>(2 * q + (dd % 1000000ULL != 0), 0xffffULL);
+  const uint32_t span = es - ss;  // (uint32: an end before the start wraps to a large value)
+  scan[3 * stride] = uint32_t(d16) | (span < 0xffffu ? span : 0xffffu) << 16;
+}
+
+// A key's dictionary as one contiguous blob in the order a workgroup stages it into LDS:
+// [value offsets nvals+1 | value bytes (whole words) | set offsets nsets+1 | set values] (set
+// arrays only for non-identity keys). The blob is assembled on the device from the key's own
+// arrays (config 4's statement dictionary is ~1 GB: building it on the host first was a zero
+// fill and a copy of that much). Returns the bytes copied to the device.
+static size_t upload_key_dict(DevBlock &d, const KeyColumn &kc, DevKey &k, hipStream_t s) {
+  k.name = kc.name;
+  k.width = kc.width();
+  k.nvals = kc.nvals();
+  k.nsets = kc.nsets();
+  k.identity = kc.identity;
+  const size_t bw = (kc.dict_bytes.size() + 3) / 4;
+  const size_t nso = kc.identity ? 0 : kc.set_off.size(), nsv = kc.identity ? 0 : kc.set_vals.size();
+  uint32_t *dblob = dev_zeroed<uint32_t>(d, kc.dict_off.size() + bw + nso + nsv, s);
+  size_t copied = 0;
+  auto put = [&](uint32_t *dst, const void *src, size_t bytes) {
+    if (bytes) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
+    copied += bytes;
+  };
+  put(dblob, kc.dict_off.data(), kc.dict_off.size() * 4);
+  put(dblob + kc.dict_off.size(), kc.dict_bytes.data(), kc.dict_bytes.size());
+  if (nso) put(dblob + kc.dict_off.size() + bw, kc.set_off.data(), nso * 4);
+  if (nsv) put(dblob + kc.dict_off.size() + bw + nso, kc.set_vals.data(), nsv * 4);
+  k.dict_off = dblob;
+  k.dict_bytes = reinterpret_cast<uint8_t *>(dblob + kc.dict_off.size());
+  k.dict_nbytes = kc.dict_bytes.size();
+  if (!kc.identity) {
+    k.set_off = dblob + kc.dict_off.size() + bw;
+    k.set_vals = k.set_off + nso;
+    k.nsetvals = uint32_t(nsv);
+  }
+  return copied;
+}
+
+// The interned dictionaries of a block's narrow keys (Block::narrow).
+static void intern_narrow_keys(Ctx &c, Block &b, const std::vector<int> &narrow_slot) {
+  const HostBlock &h = *b.host;
+  b.narrow.assign(h.keys.size(), nullptr);
+  for (size_t k = 0; k < h.keys.size(); k++) {
+    if (narrow_slot[k] < 0) continue;
+    const KeyColumn &kc = h.keys[k];
+    NarrowDict nd;
+    nd.bytes.assign(kc.dict_bytes.begin(), kc.dict_bytes.end());
+    nd.off = kc.dict_off;
+    nd.set_off = kc.set_off;
+    nd.set_vals = kc.set_vals;
+    nd.identity = kc.identity;
+    b.narrow[k] = intern_narrow(c, std::move(nd));
+  }
+}
+
 void block_upload(Ctx &c, Block &b, int device_hint) {
   if (c.devs.empty()) fail(TSG_E_DEVICE, "no device");
   DeviceCtx &dc = *c.devs[size_t(std::max(device_hint, 0)) % c.devs.size()];
@@ -216,18 +283,7 @@ void block_upload(Ctx &c, Block &b, int device_hint) {
   d.npad = npad;
   std::vector<uint32_t> scan(4 * npad, 0);
   std::vector<uint64_t> dur64(n);
-  for (size_t i = 0; i < n; i++) {
-    uint64_t dd = h.end[i] - h.start[i];  // uint64 wrap (pitfall P2)
-    dur64[i] = dd;
-    scan[i] = dd >= 0xffffffffULL ? 0xffffffffu : uint32_t(dd);
-    const uint32_t ss = uint32_t(h.start[i] / 1000000000ULL), es = uint32_t(h.end[i] / 1000000000ULL);
-    scan[npad + i] = ss;
-    scan[2 * npad + i] = es;
-    const uint64_t q = dd / 1000000ULL;
-    const uint64_t d16 = q >= 0x8000ULL ? 0xffffULL : std::min<uint64_t>(2 * q + (dd % 1000000ULL != 0), 0xffffULL);
-    const uint32_t span = es - ss;  // (uint32: an end before the start wraps to a large value)
-    scan[3 * npad + i] = uint32_t(d16) | (span < 0xffffu ? span : 0xffffu) << 16;
-  }
+  for (size_t i = 0; i < n; i++) pack_scan(h.start[i], h.end[i], scan.data() + i, npad, dur64[i]);
   // one-byte key columns: one allocation, npad bytes per narrow key
   d.narrow_slot.assign(h.keys.size(), -1);
   int nn = 0;
@@ -240,28 +296,13 @@ void block_upload(Ctx &c, Block &b, int device_hint) {
     const auto &col = h.keys[k].col;
     for (size_t i = 0; i < n; i++) dst[i] = col[i] == kNone ? 0xff : uint8_t(col[i]);
   }
-  b.narrow.assign(h.keys.size(), nullptr);
-  for (size_t k = 0; k < h.keys.size(); k++) {
-    if (d.narrow_slot[k] < 0) continue;
-    const KeyColumn &kc = h.keys[k];
-    NarrowDict nd;
-    nd.bytes.assign(kc.dict_bytes.begin(), kc.dict_bytes.end());
-    nd.off = kc.dict_off;
-    nd.set_off = kc.set_off;
-    nd.set_vals = kc.set_vals;
-    nd.identity = kc.identity;
-    b.narrow[k] = intern_narrow(c, std::move(nd));
-  }
+  intern_narrow_keys(c, b, d.narrow_slot);
   std::vector<uint32_t> names(2 * n);
   for (size_t i = 0; i < n; i++) {
     names[2 * i] = h.svc_vid.empty() ? kNone : h.svc_vid[i];
     names[2 * i + 1] = h.name_vid.empty() ? kNone : h.name_vid[i];
   }
-  // per key: its 16-bit column (width 2) and one contiguous blob in the order a workgroup
-  // stages it into LDS: [value offsets nvals+1 | value bytes (whole words) | set offsets
-  // nsets+1 | set values] (set arrays only for non-identity keys). The blob is assembled on
-  // the device from the key's own arrays (config 4's statement dictionary is ~1 GB: building
-  // it on the host first was a zero fill and a copy of that much)
+  // per key: its 16-bit column (width 2); its dictionary blob: upload_key_dict
   const size_t nk = h.keys.size();
   std::vector<std::vector<uint16_t>> col16(nk);
   for (size_t k = 0; k < nk; k++) {
@@ -292,11 +333,7 @@ void block_upload(Ctx &c, Block &b, int device_hint) {
   for (size_t kk = 0; kk < nk; kk++) {
     const KeyColumn &kc = h.keys[kk];
     DevKey k;
-    k.name = kc.name;
     k.width = kc.width();
-    k.nvals = kc.nvals();
-    k.nsets = kc.nsets();
-    k.identity = kc.identity;
     if (k.width == 1) {
       k.col = const_cast<uint8_t *>(d.narrow_base) + size_t(d.narrow_slot[kk]) * npad;
     } else if (k.width == 2) {
@@ -304,29 +341,186 @@ void block_upload(Ctx &c, Block &b, int device_hint) {
     } else {
       k.col = dev_upload(d, kc.col.data(), n, s, kColPad);
     }
-    const size_t bw = (kc.dict_bytes.size() + 3) / 4;
-    const size_t nso = kc.identity ? 0 : kc.set_off.size(), nsv = kc.identity ? 0 : kc.set_vals.size();
-    uint32_t *dblob = dev_zeroed<uint32_t>(d, kc.dict_off.size() + bw + nso + nsv, s);
-    auto put = [&](uint32_t *dst, const void *src, size_t bytes) {
-      if (bytes) HIP_OK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
-    };
-    put(dblob, kc.dict_off.data(), kc.dict_off.size() * 4);
-    put(dblob + kc.dict_off.size(), kc.dict_bytes.data(), kc.dict_bytes.size());
-    if (nso) put(dblob + kc.dict_off.size() + bw, kc.set_off.data(), nso * 4);
-    if (nsv) put(dblob + kc.dict_off.size() + bw + nso, kc.set_vals.data(), nsv * 4);
-    k.dict_off = dblob;
-    k.dict_bytes = reinterpret_cast<uint8_t *>(dblob + kc.dict_off.size());
-    k.dict_nbytes = kc.dict_bytes.size();
-    if (!kc.identity) {
-      k.set_off = dblob + kc.dict_off.size() + bw;
-      k.set_vals = k.set_off + nso;
-      k.nsetvals = uint32_t(nsv);
-    }
+    upload_key_dict(d, kc, k, s);
     d.keys.push_back(k);
   }
   // the staging vectors must outlive the async copies
   HIP_OK(hipStreamSynchronize(s));
   upload_desc(d, s);
+}
+
+// count elements, not filled (the merge kernel writes every one); the bytes that round the
+// allocation up to whole 16-byte words are zeroed as dev_upload zeroes them
+template <typename T>
+static T *dev_unfilled(DevBlock &b, size_t count, hipStream_t s) {
+  void *p = nullptr;
+  const size_t bytes = std::max<size_t>((count * sizeof(T) + 15) / 16 * 16, 16);
+  HIP_OK(hipMalloc(&p, bytes));
+  b.allocs.push_back(p);
+  b.alloc_bytes.push_back(bytes);
+  b.bytes += bytes;
+  if (bytes > count * sizeof(T))
+    HIP_OK(hipMemsetAsync(static_cast<uint8_t *>(p) + count * sizeof(T), 0, bytes - count * sizeof(T), s));
+  return static_cast<T *>(p);
+}
+
+// The device half of tsg_wal_block_refresh (the host half: block.cpp plan_wal_refresh, which
+// has filled nb.host). nb gets the allocations block_upload would make for it, in the same
+// order and with the same padding and grouping; their entry columns are written by
+// wal_merge_kernel from old's columns, the uploaded delta and the renumbering tables, the
+// dictionaries are uploaded whole (they are what changed). old is only read.
+void block_refresh(Ctx &c, const Block &old, Block &nb, const WalRefreshPlan &plan, uint64_t &upload_bytes,
+                   uint64_t &kernel_ns) {
+  if (!old.dc) fail(TSG_E_INVALID, "wal refresh: the block is not resident");
+  DeviceCtx &dc = *old.dc;
+  nb.dc = &dc;
+  DevBlock &d = nb.dev;
+  const DevBlock &o = old.dev;
+  const HostBlock &h = *nb.host;
+  d = DevBlock();
+  d.device = dc.ordinal;
+  d.n = h.n;
+  const size_t n = h.n, nd = plan.ndelta(), nk = h.keys.size(), nk_old = o.keys.size();
+  if (o.n != plan.n_old || n != plan.n_new || plan.dcol.size() != nk || plan.set_lut.size() != nk_old || nk_old > nk)
+    fail(TSG_E_INVALID, "wal refresh: the plan does not fit the block");
+  const size_t npad = (std::max<size_t>(n, 1) + kColPad - 1) / kColPad * kColPad;
+  d.npad = npad;
+  d.narrow_slot.assign(nk, -1);
+  int nn = 0;
+  for (size_t k = 0; k < nk; k++)
+    if (h.keys[k].width() == 1) d.narrow_slot[k] = nn++;
+  intern_narrow_keys(c, nb, d.narrow_slot);
+  // everything the kernel reads besides old's columns, in one staging buffer of 16-byte
+  // aligned parts: positions, the delta's columns, the tables, the jobs
+  std::vector<uint8_t> stage;
+  auto part = [&](const void *src, size_t bytes) {
+    const size_t at = stage.size();
+    stage.resize(at + (bytes + 15) / 16 * 16, 0);
+    if (bytes && src) std::memcpy(stage.data() + at, src, bytes);
+    return at;
+  };
+  std::vector<uint32_t> dpos(nd);
+  for (size_t i = 0; i < nd; i++) dpos[i] = plan.dlo[i] + plan.dins[i];
+  std::vector<uint32_t> dscan(4 * nd), dnames(2 * nd);
+  std::vector<uint64_t> ddur64(nd);
+  for (size_t i = 0; i < nd; i++) {
+    pack_scan(plan.start[i], plan.end[i], dscan.data() + i, nd, ddur64[i]);
+    dnames[2 * i] = plan.svc_vid[i];
+    dnames[2 * i + 1] = plan.name_vid[i];
+  }
+  const size_t at_pos = part(dpos.data(), nd * 4), at_ins = part(plan.dins.data(), (nd + 1) * 4);
+  const size_t at_scan = part(dscan.data(), dscan.size() * 4), at_dur64 = part(ddur64.data(), nd * 8);
+  const size_t at_ids = part(plan.ids.data(), nd * 16), at_idlen = part(plan.id_len.data(), nd);
+  const size_t at_start = part(plan.start.data(), nd * 8), at_end = part(plan.end.data(), nd * 8);
+  const size_t at_names = part(dnames.data(), dnames.size() * 4);
+  const size_t at_svc = part(plan.svc_lut.data(), plan.svc_lut.size() * 4);
+  const size_t at_name = part(plan.name_lut.data(), plan.name_lut.size() * 4);
+  std::vector<size_t> at_dcol(nk), at_lut(nk_old);
+  for (size_t k = 0; k < nk; k++) at_dcol[k] = part(plan.dcol[k].data(), nd * 4);
+  for (size_t k = 0; k < nk_old; k++) at_lut[k] = part(plan.set_lut[k].data(), plan.set_lut[k].size() * 4);
+  const size_t njobs = 8 + nk;
+  const size_t at_jobs = part(nullptr, njobs * sizeof(WalMergeJob));
+
+  std::lock_guard<std::mutex> lk(dc.mu);
+  dc.mem_epoch++;  // (the new block's columns: a resident search launch relaunches before it reads them)
+  resident_quit(dc);
+  HIP_OK(hipSetDevice(dc.ordinal));
+  hipStream_t s = dc.stream;
+  upload_bytes = 0;
+  // the allocations, in block_upload's order
+  d.dur32 = dev_unfilled<uint32_t>(d, 4 * npad, s);
+  d.start_s = d.dur32 + npad;
+  d.end_s = d.dur32 + 2 * npad;
+  d.dur64 = dev_unfilled<uint64_t>(d, n, s);
+  uint8_t *narrow = dev_unfilled<uint8_t>(d, std::max<size_t>(size_t(nn), 1) * npad, s);
+  if (!nn) HIP_OK(hipMemsetAsync(narrow, 0xff, npad, s));
+  d.narrow_base = narrow;
+  d.ids = dev_unfilled<uint8_t>(d, n * 16, s);
+  d.start_ns = dev_unfilled<uint64_t>(d, n, s);
+  d.end_ns = dev_unfilled<uint64_t>(d, n, s);
+  d.names = dev_unfilled<uint32_t>(d, 2 * n, s);
+  d.id_len = dev_unfilled<uint8_t>(d, n, s);
+  for (size_t kk = 0; kk < nk; kk++) {
+    const KeyColumn &kc = h.keys[kk];
+    DevKey k;
+    k.width = kc.width();
+    if (k.width == 1) k.col = narrow + size_t(d.narrow_slot[kk]) * npad;
+    else if (k.width == 2) k.col = dev_unfilled<uint16_t>(d, npad, s);
+    else k.col = dev_unfilled<uint32_t>(d, npad, s);
+    upload_bytes += upload_key_dict(d, kc, k, s);
+    d.keys.push_back(k);
+  }
+  // the jobs, now that both sides' addresses are known
+  DevBuf dstage;  // (this call's only: released below, on an error once the stream has drained)
+  try {
+    dstage.ensure(stage.size());
+    const uint8_t *base = static_cast<const uint8_t *>(dstage.p);
+    auto dev = [&](size_t at) { return static_cast<const void *>(base + at); };
+    auto *jobs = reinterpret_cast<WalMergeJob *>(stage.data() + at_jobs);
+    size_t nj = 0;
+    auto job = [&](uint32_t kind, const void *src, void *dst, const void *delta, uint32_t wo, uint32_t wn) -> WalMergeJob & {
+      WalMergeJob &j = jobs[nj++];
+      j = WalMergeJob();
+      j.kind = kind;
+      j.src = src;
+      j.dst = dst;
+      j.delta = delta;
+      j.wo = wo;
+      j.wn = wn;
+      return j;
+    };
+    WalMergeJob &js = job(WalMergeJob::kScan, o.dur32, d.dur32, dev(at_scan), 4, 4);
+    js.src_stride = o.npad;
+    js.dst_stride = npad;
+    job(WalMergeJob::kCopy, o.dur64, d.dur64, dev(at_dur64), 8, 8);
+    job(WalMergeJob::kCopy, o.ids, d.ids, dev(at_ids), 16, 16);
+    job(WalMergeJob::kCopy, o.start_ns, d.start_ns, dev(at_start), 8, 8);
+    job(WalMergeJob::kCopy, o.end_ns, d.end_ns, dev(at_end), 8, 8);
+    job(WalMergeJob::kCopy, o.id_len, d.id_len, dev(at_idlen), 1, 1);
+    WalMergeJob &jn = job(WalMergeJob::kNames, o.names, d.names, dev(at_names), 8, 8);
+    if (!plan.svc_lut.empty()) {
+      jn.lut = static_cast<const uint32_t *>(dev(at_svc));
+      jn.lut_n = uint32_t(plan.svc_lut.size());
+    }
+    if (!plan.name_lut.empty()) {
+      jn.lut2 = static_cast<const uint32_t *>(dev(at_name));
+      jn.lut2_n = uint32_t(plan.name_lut.size());
+    }
+    for (size_t k = 0; k < nk; k++) {
+      const bool had = k < nk_old;
+      WalMergeJob &jt = job(WalMergeJob::kTerm, had ? o.keys[k].col : nullptr, d.keys[k].col, dev(at_dcol[k]),
+                            had ? uint32_t(o.keys[k].width) : 0u, uint32_t(d.keys[k].width));
+      if (had && !plan.set_lut[k].empty()) {
+        jt.lut = static_cast<const uint32_t *>(dev(at_lut[k]));
+        jt.lut_n = uint32_t(plan.set_lut[k].size());
+      }
+    }
+    HIP_OK(hipMemcpyAsync(dstage.p, stage.data(), stage.size(), hipMemcpyHostToDevice, s));
+    upload_bytes += stage.size();
+    WalMergeArgs a{};
+    a.jobs = static_cast<const WalMergeJob *>(dev(at_jobs));
+    a.njobs = uint32_t(nj);
+    a.dpos = static_cast<const uint32_t *>(dev(at_pos));
+    a.dins = static_cast<const uint32_t *>(dev(at_ins));
+    a.ndelta = uint32_t(nd);
+    a.n_old = o.n;
+    a.n_new = n;
+    a.npad = npad;
+    HIP_OK(hipEventRecord(dc.ev0, s));
+    wal_merge_launch(a, s);
+    HIP_OK(hipEventRecord(dc.ev1, s));
+    HIP_OK(hipStreamSynchronize(s));  // (the staging vectors must outlive the async copies)
+    float ms = 0;
+    HIP_OK(hipEventElapsedTime(&ms, dc.ev0, dc.ev1));
+    kernel_ns = uint64_t(double(ms) * 1e6);
+  } catch (...) {
+    (void)hipStreamSynchronize(s);
+    dstage.release();
+    throw;
+  }
+  dstage.release();
+  upload_desc(d, s);
+  upload_bytes += sizeof(DevBlockDesc) + d.keys.size() * sizeof(DevKeyDesc);
 }
 
 // resident descriptor (one-launch search path): the block's column and dictionary pointers

@@ -119,6 +119,13 @@ void block_upload(Ctx &c, Block &b, int device_hint);
 // by value): replicas for load balancing across GPUs, or disjoint copies of one data set.
 void block_clone(Ctx &c, const Block &src, Block &dst, int device_hint);
 void block_free(Block &b);
+// tsg_wal_block_refresh's device half (devctx.hip): nb.host is the new block's host side
+// (plan_wal_refresh); nb's columns are written on old's device from old's columns and the
+// plan's delta (wal_merge_kernel). upload_bytes: host-to-device bytes of the call. Weak: a
+// host-only build of the library (the sanitizer stand-in for the device) links without it,
+// and the refresh then reports TSG_E_DEVICE.
+void block_refresh(Ctx &c, const Block &old, Block &nb, const WalRefreshPlan &plan, uint64_t &upload_bytes,
+                   uint64_t &kernel_ns) __attribute__((weak));
 
 struct SearchOut {
   struct Rec {

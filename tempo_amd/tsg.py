@@ -154,11 +154,17 @@ class _LookupResult(C.Structure):
                 ("record_length", C.POINTER(C.c_uint32)), ("kernel_ns", C.c_uint64)]
 
 
+class _WalRefreshStats(C.Structure):
+    _fields_ = [("bytes_replayed", C.c_uint64), ("pages_replayed", C.c_uint64), ("entries_added", C.c_uint64),
+                ("entries_combined", C.c_uint64), ("upload_bytes", C.c_uint64), ("kernel_ns", C.c_uint64),
+                ("mode", C.c_int32)]
+
+
 # Every symbol include/tsg.h declares (checked by tests/test_abi.py).
 EXPORTED = [
     "tsg_init", "tsg_shutdown", "tsg_device_count", "tsg_device_numa_node", "tsg_device_counters", "tsg_last_error", "tsg_abi_version", "tsg_cancel",
     "tsg_pipeline_new", "tsg_pipeline_query", "tsg_pipeline_free", "tsg_pipeline_matches_header",
-    "tsg_block_open", "tsg_block_open_pages", "tsg_block_open_mem", "tsg_block_clone", "tsg_wal_block_open", "tsg_wal_block_open_mem", "tsg_block_close", "tsg_block_info_get", "tsg_block_tags",
+    "tsg_block_open", "tsg_block_open_pages", "tsg_block_open_mem", "tsg_block_clone", "tsg_wal_block_open", "tsg_wal_block_open_mem", "tsg_wal_block_refresh", "tsg_wal_block_refresh_mem", "tsg_block_close", "tsg_block_info_get", "tsg_block_tags",
     "tsg_block_tag_values", "tsg_free", "tsg_search", "tsg_result_free", "tsg_kernel_times", "tsg_results_combine",
     "tsg_v2block_open", "tsg_v2block_close", "tsg_lookup_ids", "tsg_lookup_result_free", "tsg_find_ids",
     "tsg_find_result_free", "tsg_proto_block_open", "tsg_proto_block_close", "tsg_proto_block_info",
@@ -198,6 +204,9 @@ def lib():
         L.tsg_block_clone.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
         L.tsg_wal_block_open.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(vp)]
         L.tsg_wal_block_open_mem.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.POINTER(vp)]
+        L.tsg_wal_block_refresh.argtypes = [vp, vp, C.c_char_p, C.POINTER(vp), C.POINTER(_WalRefreshStats)]
+        L.tsg_wal_block_refresh_mem.argtypes = [vp, vp, C.c_char_p, C.c_size_t, C.POINTER(vp),
+                                                C.POINTER(_WalRefreshStats)]
         L.tsg_write_wal_search.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, C.c_int]
         L.tsg_block_info_get.argtypes = [vp, C.POINTER(_BlockInfo)]
         L.tsg_live_block_open_mem.argtypes = [vp, C.c_char_p, vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.POINTER(vp)]
@@ -437,6 +446,24 @@ class Engine:
     def open_wal_block(self, path: str, device: int = 0) -> "StreamingSearchBlock":
         """Replay a search WAL file (<blockID>:<tenant>:v2:<encoding>[:...]) onto a device."""
         return StreamingSearchBlock(self, path, device)
+
+    def refresh_wal_block(self, old: "BackendSearchBlock", path_or_bytes):
+        """tsg_wal_block_refresh[_mem]: `old`'s WAL file has grown (a path, or the file's bytes).
+        Returns (block, stats): a new handle equal to open_wal_block of the file as it is now, on
+        old's device, and the call's tsg_wal_refresh_stats as a dict (mode 1 incremental, 0 nothing
+        new, 2 full reopen). `old` stays open and searchable: close it once the new handle is in use."""
+        blk = StreamingSearchBlock.__new__(StreamingSearchBlock)
+        blk.path = path_or_bytes if isinstance(path_or_bytes, str) else getattr(old, "path", None)
+        blk.pages = None
+        blk.h = C.c_void_p()
+        st = _WalRefreshStats()
+        if isinstance(path_or_bytes, str):
+            _check(lib().tsg_wal_block_refresh(self.h, old.h, path_or_bytes.encode(), C.byref(blk.h), C.byref(st)))
+        else:
+            data = bytes(path_or_bytes)
+            _check(lib().tsg_wal_block_refresh_mem(self.h, old.h, data, len(data), C.byref(blk.h), C.byref(st)))
+        self._open.add(blk)
+        return blk, {f: getattr(st, f) for f, _ in _WalRefreshStats._fields_}
 
     def open_block(self, path: str, device: int = 0, pages=None) -> "BackendSearchBlock":
         """A backend search block resident on `device`; pages = (first_page, npages): only that
