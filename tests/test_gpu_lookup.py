@@ -67,7 +67,9 @@ def test_time_and_block_range(engine, tmp_path):
 def test_ids_in_many_blocks(engine, tmp_path):
     """The same block set opened 7 times: every present id hits 7 blocks, more than
     the count pass keeps per id (4), so the write pass re-probes those ids; ids with
-    <= 4 hits are copied. Both must give the oracle's (id, block) order."""
+    <= 4 hits are copied. Both must give the oracle's (id, block) order. This covers repeated
+    blocks only (members with identical blooms and records, where a swapped member column
+    returns the same hits); slabs of distinct members are in tests/test_gpu_lookup_edges.py."""
     paths = []
     for b in range(2):
         p = os.path.join(str(tmp_path), "m%d" % b)
