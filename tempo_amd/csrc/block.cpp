@@ -534,9 +534,13 @@ struct PageHint {
   size_t tables = 0, vals = 0, refs = 0;
 };
 
+// decoded (optional): the page's decoded bytes, already checked by whoever decoded them (a decoder
+// that runs elsewhere, e.g. on the device, hands its pages in here); otherwise the page is read
+// and decoded here. Everything behind the decode is one code.
 void parse_lpage(const uint8_t *data, size_t dlen, int enc, const IndexRecord &rec, KeyNames &kn, KeyCache &kc,
-                 PosMap &pm, PageHint &hint, LPage &pp) {
-  read_data_page(data, dlen, rec, enc, pp.buf);
+                 PosMap &pm, PageHint &hint, LPage &pp, const uint8_t *decoded = nullptr, size_t decoded_len = 0) {
+  if (decoded) pp.buf.assign(decoded, decoded + decoded_len);  // (the views below outlive the caller's buffer)
+  else read_data_page(data, dlen, rec, enc, pp.buf);
   // object.UnmarshalAndAdvanceBuffer (object.go:82-113): [u32 total][u32 idLen][id][obj]
   if (pp.buf.size() < 8) fail(TSG_E_CORRUPT, "object header truncated");
   const uint32_t total = le32(pp.buf.data()), il = le32(pp.buf.data() + 4);
