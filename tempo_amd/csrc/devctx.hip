@@ -13,6 +13,7 @@
 
 #include "aql.hpp"
 #include "devctx.hpp"
+#include "ds_word.hpp"
 #include "wal_merge.hpp"
 
 namespace tsg {
@@ -197,18 +198,28 @@ static std::shared_ptr<const NarrowDict> intern_narrow(Ctx &c, NarrowDict &&nd) 
 }
 
 // One entry's scan columns: scan[0], scan[stride], scan[2 * stride], scan[3 * stride] = dur32,
-// start_s, end_s, ds (block_upload describes ds); dur64 = the exact duration.
-static inline void pack_scan(uint64_t start, uint64_t end, uint32_t *scan, size_t stride, uint64_t &dur64) {
+// start_s, end_s, ds (the packed scan word against the block's base: ds_word.hpp); dur64 = the
+// exact duration.
+static inline void pack_scan(uint64_t start, uint64_t end, uint32_t base, uint32_t *scan, size_t stride,
+                             uint64_t &dur64) {
   const uint64_t dd = end - start;  // uint64 wrap (pitfall P2)
   dur64 = dd;
   scan[0] = dd >= 0xffffffffULL ? 0xffffffffu : uint32_t(dd);
   const uint32_t ss = uint32_t(start / 1000000000ULL), es = uint32_t(end / 1000000000ULL);
   scan[stride] = ss;
   scan[2 * stride] = es;
-  const uint64_t q = dd / 1000000ULL;
-  const uint64_t d16 = q >= 0x8000ULL ? 0xffffULL : std::min<uint64_t>(2 * q + (dd % 1000000ULL != 0), 0xffffULL);
-  const uint32_t span = es - ss;  // (uint32: an end before the start wraps to a large value)
-  scan[3 * stride] = uint32_t(d16) | (span < 0xffffu ? span : 0xffffu) << 16;
+  scan[3 * stride] = ds_pack(start, end, base);
+}
+
+// The base of a block's packed scan words: its median start second less half the 15-bit window
+// (outlier starts do not move it; they escape to the exact column).
+static uint32_t scan_base(const std::vector<uint64_t> &start) {
+  if (start.empty()) return 0;
+  std::vector<uint32_t> ss(start.size());
+  for (size_t i = 0; i < start.size(); i++) ss[i] = uint32_t(start[i] / 1000000000ULL);
+  auto mid = ss.begin() + ss.size() / 2;
+  std::nth_element(ss.begin(), mid, ss.end());
+  return ds_base(*mid);
 }
 
 // A key's dictionary as one contiguous blob in the order a workgroup stages it into LDS:
@@ -274,16 +285,18 @@ void block_upload(Ctx &c, Block &b, int device_hint) {
   // Every host-side array is built first, without the device lock (blocks opened together
   // prepare theirs concurrently); the lock is held for the allocations and copies only.
   // [dur32 | start_s | end_s | ds], npad entries each (whole tiles: kColPad), one allocation.
-  // ds, the pool kernels' compact form of the other three (4 B where they read 12):
+  // ds, the pool kernels' compact form of the other three (4 B where they read 12; ds_word.hpp):
   //   bits 0..15  D16 = 2 * floor(dur / 1 ms) + (dur % 1 ms != 0), saturated at 0xffff: for whole-
   //               ms bounds m, M <= kDs16MaxMs, dur >= m ms <=> D16 >= 2m and dur <= M ms <=> D16 <= 2M
   //               (a saturated entry has dur >= 32767 ms: above every such M, not below any m)
-  //   bits 16..31 end_s - start_s when it fits below 0xffff, else 0xffff (the kernel then reads end_s)
+  //   bit  16     (end_s - start_s) - floor(dur / 1 s), 0 when D16 is saturated (the kernel then reads end_s)
+  //   bits 17..31 start_s - sbase when it fits below 0x7fff, else 0x7fff (the kernel then reads start_s)
   const size_t npad = (std::max<size_t>(n, 1) + kColPad - 1) / kColPad * kColPad;
   d.npad = npad;
   std::vector<uint32_t> scan(4 * npad, 0);
   std::vector<uint64_t> dur64(n);
-  for (size_t i = 0; i < n; i++) pack_scan(h.start[i], h.end[i], scan.data() + i, npad, dur64[i]);
+  d.sbase = scan_base(h.start);
+  for (size_t i = 0; i < n; i++) pack_scan(h.start[i], h.end[i], d.sbase, scan.data() + i, npad, dur64[i]);
   // one-byte key columns: one allocation, npad bytes per narrow key
   d.narrow_slot.assign(h.keys.size(), -1);
   int nn = 0;
@@ -380,6 +393,9 @@ void block_refresh(Ctx &c, const Block &old, Block &nb, const WalRefreshPlan &pl
   d = DevBlock();
   d.device = dc.ordinal;
   d.n = h.n;
+  // the old block's base: its entries' ds words are copied as they are and the delta is packed
+  // against it (later entries outside the window escape to the exact start column)
+  d.sbase = o.sbase;
   const size_t n = h.n, nd = plan.ndelta(), nk = h.keys.size(), nk_old = o.keys.size();
   if (o.n != plan.n_old || n != plan.n_new || plan.dcol.size() != nk || plan.set_lut.size() != nk_old || nk_old > nk)
     fail(TSG_E_INVALID, "wal refresh: the plan does not fit the block");
@@ -404,7 +420,7 @@ void block_refresh(Ctx &c, const Block &old, Block &nb, const WalRefreshPlan &pl
   std::vector<uint32_t> dscan(4 * nd), dnames(2 * nd);
   std::vector<uint64_t> ddur64(nd);
   for (size_t i = 0; i < nd; i++) {
-    pack_scan(plan.start[i], plan.end[i], dscan.data() + i, nd, ddur64[i]);
+    pack_scan(plan.start[i], plan.end[i], d.sbase, dscan.data() + i, nd, ddur64[i]);
     dnames[2 * i] = plan.svc_vid[i];
     dnames[2 * i + 1] = plan.name_vid[i];
   }
@@ -603,6 +619,7 @@ void block_clone(Ctx &c, const Block &src, Block &dst, int device_hint) {
   d.names = static_cast<uint32_t *>(xl(o.names));
   d.id_len = static_cast<uint8_t *>(xl(o.id_len));
   d.npad = o.npad;
+  d.sbase = o.sbase;  // (the ds column is copied verbatim)
   d.narrow_base = static_cast<const uint8_t *>(xl(o.narrow_base));
   d.narrow_slot = o.narrow_slot;
   dst.narrow = src.narrow;

@@ -85,6 +85,7 @@ struct DevBlock {
   // dur32 | start_s | end_s share one allocation, `npad` entries each; the one-byte key
   // columns share another, `npad` bytes per slot (narrow_slot[k], -1 for wider keys)
   uint64_t npad = 0;
+  uint32_t sbase = 0;  // the base second of the packed scan words (ds_word.hpp), fixed at upload
   const uint8_t *narrow_base = nullptr;
   std::vector<int> narrow_slot;
   std::vector<DevKey> keys;

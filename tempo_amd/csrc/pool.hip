@@ -571,7 +571,7 @@ static uint32_t slot_of(const std::vector<uint32_t> &pos, const SearchOut::Rec &
 template <class Each>
 static void finish_records(SearchOut &out, const std::vector<uint32_t> &pos, const std::vector<ScanSeg> &segs,
                            const std::vector<std::pair<uint32_t, Block *>> &blocks, uint32_t limit, uint64_t total,
-                           uint32_t W, bool ds_and_start, Each &&each) {
+                           uint32_t W, bool has_dur, bool has_range, Each &&each) {
   thread_local std::vector<uint64_t> per;
   per.assign(segs.size(), 0);
   out.recs.resize(total);
@@ -594,9 +594,9 @@ static void finish_records(SearchOut &out, const std::vector<uint32_t> &pos, con
       if (blocks[bi].first == segs[i].block_idx) out.block_counts[bi] = per[i];
   out.scan_bytes += uint64_t(W) * 4 + kept * 32;  // + workgroup counts, + id/start/end of each record
   // (the caller counted 4 B of duration + 8 B of start / end per entry; these kernels read
-  // the 4 B ds column (duration | span) + the 4 B start column when both filters are on)
-  if (ds_and_start)
-    for (const auto &sg : segs) out.scan_bytes -= 4ull * (sg.n - sg.e0);
+  // the one 4 B packed scan word (ds_word.hpp) when either filter is on)
+  const uint64_t counted = (has_dur ? 4u : 0u) + (has_range ? 8u : 0u), read = counted ? 4u : 0u;
+  for (const auto &sg : segs) out.scan_bytes -= (counted - read) * (sg.n - sg.e0);
 }
 
 // The resident path of pool_search: 1 = served (out filled), 0 = the records overflowed (the
@@ -844,7 +844,7 @@ static int resident_search(DeviceCtx &dc, std::unique_lock<std::mutex> &lk, Pool
   // wave's matches in scan order); a limit keeps each block part's first L
   const uint32_t seg = PA.seg_cap;
   const auto *prec = reinterpret_cast<const SearchOut::Rec *>(recs);
-  finish_records(out, block_slots(segs), segs, blocks, limit, total, W, has_dur && q.has_range, [&](auto &&f) {
+  finish_records(out, block_slots(segs), segs, blocks, limit, total, W, has_dur, q.has_range != 0, [&](auto &&f) {
     for (uint32_t w = 0; w < W; w++) {
       const SearchOut::Rec *r = prec + uint64_t(w) * seg;
       for (uint32_t i = 0, c = counts[size_t(w) * cs]; i < c; i++) f(r[i]);
@@ -891,6 +891,7 @@ bool pool_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>> 
     PA.desc[i] = seg_desc[i];
     PA.ubase[i] = U;
     PA.ebase[i] = uint32_t(segs[i].e0);  // (a multiple of kPoolTile)
+    PA.sbase[i] = ns.sbase;
     const uint64_t u = (segs[i].n - segs[i].e0 + kPoolTile - 1) / kPoolTile;
     if (uint64_t(U) + u >= (1ull << 31)) return false;
     U += uint32_t(u);
@@ -1161,7 +1162,7 @@ bool pool_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>> 
   }
   // (the sorted records of a block are contiguous)
   tr.mark("post.sort");
-  finish_records(out, pos, segs, blocks, limit, total, W, has_dur && q.has_range, [&](auto &&f) {
+  finish_records(out, pos, segs, blocks, limit, total, W, has_dur, q.has_range != 0, [&](auto &&f) {
     for (uint64_t i = 0; i < total; i++) f(prec[sorted[i] & 0xfffffu]);
   });
   tr.mark("post");

@@ -5,6 +5,7 @@
 
 #include <cstddef>
 
+#include "ds_word.hpp"
 #include "search_common.hpp"
 
 namespace tsg {
@@ -37,7 +38,7 @@ constexpr size_t kPoolLds = 96 << 10;
 static_assert(kColPad % kPoolTile == 0, "column padding covers whole units");
 
 struct PoolBlk {           // 64 B, staged in LDS
-  const uint32_t *scan;    // dur32 | start_s | end_s | ds, npad entries each (the pool reads ds, start_s)
+  const uint32_t *scan;    // dur32 | start_s | end_s | ds, npad entries each (the pool reads ds; escapes the exact ones)
   const uint8_t *col[4];   // one-byte term columns
   uint32_t npad, nent;
   uint32_t ubase;          // first unit of the block in the launch's unit space
@@ -51,6 +52,7 @@ struct PoolArgs {
   uint32_t bms[kArgBms][8];
   uint32_t ubase[kArgSegs + 1];  // first unit of each block, units at nsegs (static kernel's block walk)
   uint32_t ebase[kArgSegs];      // scan position of each block's first unit (a limit wave's part of a block)
+  uint32_t sbase[kArgSegs];      // each block's base second of its packed scan words (ds_word.hpp)
   uint32_t nsegs, units, static_per_wg, dyn0;  // static run of workgroup w: [w*S, w*S+S); dynamic [dyn0, units)
   uint32_t chunk_shift, lookahead, rec_cap, seg_cap, has_min, has_max, min32, max32, start_s, end_s;
   unsigned *head;       // this launch's dynamic-chunk counter (zero at launch)
@@ -81,13 +83,13 @@ struct PoolArgs {
 static_assert(sizeof(PoolArgs) <= 4096, "kernel arguments");
 
 // The argument words a query with nsegs blocks and nbms bitmaps uses, as kArgRanges byte ranges
-// of PoolArgs: the block table, descriptors, bitmaps, unit and entry bases, and the scalars from
+// of PoolArgs: the block table, descriptors, bitmaps, unit, entry and start bases, and the scalars from
 // `nsegs` on. The host writes only those (a mailbox slot, an AQL packet of our own) and the
 // resident kernel's slot checksum covers exactly them: all three read this one description.
 struct ArgRange {
   uint32_t off, len;
 };
-constexpr int kArgRanges = 6;
+constexpr int kArgRanges = 7;
 __host__ __device__ inline ArgRange arg_range(int i, uint32_t nsegs, uint32_t nbms) {
   switch (i) {
     case 0: return {uint32_t(offsetof(PoolArgs, blk)), nsegs * uint32_t(sizeof(PoolBlk))};
@@ -95,6 +97,7 @@ __host__ __device__ inline ArgRange arg_range(int i, uint32_t nsegs, uint32_t nb
     case 2: return {uint32_t(offsetof(PoolArgs, bms)), nbms * 32u};
     case 3: return {uint32_t(offsetof(PoolArgs, ubase)), (nsegs + 1) * 4u};
     case 4: return {uint32_t(offsetof(PoolArgs, ebase)), nsegs * 4u};
+    case 5: return {uint32_t(offsetof(PoolArgs, sbase)), nsegs * 4u};
     default: return {uint32_t(offsetof(PoolArgs, nsegs)), uint32_t(sizeof(PoolArgs) - offsetof(PoolArgs, nsegs))};
   }
 }
@@ -131,7 +134,7 @@ __device__ __forceinline__ uint32_t block_of(const uint32_t *ubase, uint32_t nse
 // A unit's filter columns in registers (wave-uniform e0: the unit's first entry in its block).
 template <int NT>
 struct UnitRegs {
-  u32x4 d[kSteps], s[kSteps];  // ds (duration | span), start seconds
+  u32x4 d[kSteps];  // ds: the packed scan word (duration | carry | relative start)
   uint32_t tv[NT > 0 ? NT : 1][kSteps];
   uint32_t e0;
 };
@@ -159,7 +162,6 @@ __device__ __forceinline__ void load_unit(UnitRegs<NT> &R, const uint32_t *scan,
   for (int k = 0; k < kSteps; k++) {
     const uint64_t e = uint64_t(e0) + uint64_t(k) * 256 + uint64_t(lane) * 4;
     if (DUR || RANGE) R.d[k] = stream4<NTL>(scan + 3ull * npad, e);
-    if (RANGE) R.s[k] = stream4<NTL>(scan + npad, e);
   }
 #pragma unroll
   for (int q = 0; q < (NT > 0 ? NT : 1); q++) {
@@ -212,7 +214,7 @@ __device__ __forceinline__ uint32_t cap_unit_mask(uint32_t mask, uint32_t cap, i
 // test is evaluated for every entry and combined with bitwise ands (short-circuit tests
 // compiled to ~130 exec-mask branches per unit; with real, mixed values the lanes diverge
 // and the 150 MB scan ran 8 us longer than with uniform data, profiles/r03_launch).
-// ds: the compact duration | span column (devctx.hip), sv / ev: start / end seconds;
+// ds: the packed scan word column (ds_word.hpp), sv / ev: start / end seconds (unit_ends);
 // lo/hi: the duration bounds in ds's units (0 / 2^32-1 when a side is absent); bm: the LDS
 // bitmaps.
 template <int NT, bool DUR, bool RANGE>
@@ -254,23 +256,28 @@ __device__ __forceinline__ uint32_t unit_mask(const u32x4 (&d)[kSteps], const u3
 // counted by vmcnt. (asm memory clobber: no LDS access moves across it)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
-// End seconds of a unit's entries: start + span from the ds column, or, for a lane's four
-// entries of a step where some span did not fit 16 bits (ends 18 h or more after the start,
-// or before it: the escape 0xffff, e.g. the end = 0 entries of pitfall P1), those four from
-// the exact end column (rare; only the lanes that need them load: a unit-wide reload moved
-// 16 MB more per config-2 query, the PMC count in profiles/r04_final).
+// Start and end seconds of a unit's entries, decoded from the ds column against the block's
+// base second (ds_word.hpp): start = base + rel, end = start + whole seconds of the duration +
+// carry. For a lane's four entries of a step where some start lies outside the 15-bit window
+// (rel 0x7fff) those four starts come from the exact start column, and where some duration
+// code is saturated (0xffff: durations from 32.768 s, ends before the start, e.g. the end = 0
+// entries of pitfall P1) those four ends from the exact end column (rare; only the lanes that
+// need them load: a unit-wide reload moved 16 MB more per config-2 query, the PMC count in
+// profiles/r04_final).
 template <bool NTL>
-__device__ __forceinline__ void unit_ends(const u32x4 (&ds)[kSteps], const u32x4 (&sv)[kSteps], u32x4 (&ev)[kSteps],
-                                          const uint32_t *scan, uint32_t npad, uint32_t e0, int lane) {
+__device__ __forceinline__ void unit_ends(const u32x4 (&ds)[kSteps], uint32_t sbase, u32x4 (&sv)[kSteps],
+                                          u32x4 (&ev)[kSteps], const uint32_t *scan, uint32_t npad, uint32_t e0,
+                                          int lane) {
 #pragma unroll
   for (int k = 0; k < kSteps; k++) {
-    const uint32_t sp[4] = {ds[k].x >> 16, ds[k].y >> 16, ds[k].z >> 16, ds[k].w >> 16};
-    const bool esc = sp[0] == 0xffffu || sp[1] == 0xffffu || sp[2] == 0xffffu || sp[3] == 0xffffu;
-    ev[k].x = sv[k].x + sp[0];
-    ev[k].y = sv[k].y + sp[1];
-    ev[k].z = sv[k].z + sp[2];
-    ev[k].w = sv[k].w + sp[3];
-    if (esc) ev[k] = stream4<NTL>(scan + 2ull * npad, uint64_t(e0) + uint64_t(k) * 256 + uint64_t(lane) * 4);
+    const uint32_t w[4] = {ds[k].x, ds[k].y, ds[k].z, ds[k].w};
+    const bool esc_s = ds_start_escaped(w[0]) || ds_start_escaped(w[1]) || ds_start_escaped(w[2]) || ds_start_escaped(w[3]);
+    const bool esc_e = ds_end_escaped(w[0]) || ds_end_escaped(w[1]) || ds_end_escaped(w[2]) || ds_end_escaped(w[3]);
+    const uint64_t e = uint64_t(e0) + uint64_t(k) * 256 + uint64_t(lane) * 4;
+    sv[k] = u32x4{ds_start(w[0], sbase), ds_start(w[1], sbase), ds_start(w[2], sbase), ds_start(w[3], sbase)};
+    if (esc_s) sv[k] = stream4<NTL>(scan + npad, e);
+    ev[k] = u32x4{ds_end(w[0], sv[k].x), ds_end(w[1], sv[k].y), ds_end(w[2], sv[k].z), ds_end(w[3], sv[k].w)};
+    if (esc_e) ev[k] = stream4<NTL>(scan + 2ull * npad, e);
   }
 }
 
@@ -360,7 +367,7 @@ template <int NT, bool DUR, bool RANGE, bool NTL>
 __global__ void __launch_bounds__(kPoolThreads, 1) search_pool_kernel(PoolArgs A) {
   const unsigned long long t_start = A.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;
   __shared__ __attribute__((aligned(16))) PoolBlk s_blk[kArgSegs];
-  __shared__ uint32_t s_ub[kArgSegs + 1];
+  __shared__ uint32_t s_ub[kArgSegs + 1], s_sb[kArgSegs];
   __shared__ uint32_t s_bm[kArgBms * 8];
   __shared__ uint32_t s_chunk[kPoolChunks];
   __shared__ uint32_t s_next, s_nrec;
@@ -393,6 +400,7 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_pool_kernel(PoolArgs A
   const uint32_t *blk_words = reinterpret_cast<const uint32_t *>(A.blk);
   const uint32_t xblk = uint32_t(tid) < nsegs * 16 ? blk_words[tid] : 0u;
   const uint32_t xub = uint32_t(tid) < nsegs ? A.blk[tid].ubase : units;
+  const uint32_t xsb = uint32_t(tid) < nsegs ? A.sbase[tid] : 0u;
   const uint32_t xbm = tid < kArgBms * 8 ? reinterpret_cast<const uint32_t *>(A.bms)[tid] : 0u;
   const bool pre0 = wv < S, pre1 = wv + nwv < S;
   uint32_t ua = kPoolNone, ub = kPoolNone;
@@ -406,6 +414,7 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_pool_kernel(PoolArgs A
     static_assert(kArgSegs * 16 <= kPoolThreads && kArgBms * 8 <= kPoolThreads, "one staging word per thread");
     if (uint32_t(tid) < nsegs * 16) reinterpret_cast<uint32_t *>(s_blk)[tid] = xblk;
     if (uint32_t(tid) <= nsegs) s_ub[tid] = xub;
+    if (uint32_t(tid) < nsegs) s_sb[tid] = xsb;
     if (tid < kArgBms * 8) s_bm[tid] = xbm;
     for (uint32_t i = tid; i < kPoolChunks; i += A.nthreads) s_chunk[i] = kPoolPending;
     if (tid == 0) {
@@ -486,9 +495,9 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_pool_kernel(PoolArgs A
   auto eval = [&](const Unit &R) {
     const PoolBlk &B = s_blk[R.blk];
     const uint32_t n = rfl(B.nent), bmi4 = rfl(B.bmi4), ns4 = rfl(B.nsets4);
-    u32x4 ev[kSteps];
-    if (RANGE) unit_ends<NTL>(R.d, R.s, ev, uniform_ptr(B.scan), rfl(B.npad), R.e0, lane);
-    uint32_t mask = unit_mask<NT, DUR, RANGE>(R.d, R.s, ev, R.tv, R.e0, n, dlo, dhi, A.start_s, A.end_s, bmi4,
+    u32x4 sv[kSteps], ev[kSteps];
+    if (RANGE) unit_ends<NTL>(R.d, rfl(s_sb[R.blk]), sv, ev, uniform_ptr(B.scan), rfl(B.npad), R.e0, lane);
+    uint32_t mask = unit_mask<NT, DUR, RANGE>(R.d, sv, ev, R.tv, R.e0, n, dlo, dhi, A.start_s, A.end_s, bmi4,
                                                ns4, s_bm, lane);
     if (__ballot(mask != 0) == 0) return;
     if (A.unit_cap) mask = cap_unit_mask(mask, A.unit_cap, lane);
@@ -582,9 +591,9 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_static_kernel(PoolArgs
   auto eval = [&](const Unit &R, uint32_t bslot) {
     const PoolBlk &P = A.blk[bslot];
     const uint32_t n = P.nent, bmi4 = P.bmi4, ns4 = P.nsets4;
-    u32x4 ev[kSteps];
-    if (RANGE) unit_ends<NTL>(R.d, R.s, ev, P.scan, P.npad, R.e0, lane);
-    uint32_t mask = unit_mask<NT, DUR, RANGE>(R.d, R.s, ev, R.tv, R.e0, n, dlo, dhi, A.start_s, A.end_s, bmi4,
+    u32x4 sv[kSteps], ev[kSteps];
+    if (RANGE) unit_ends<NTL>(R.d, A.sbase[bslot], sv, ev, P.scan, P.npad, R.e0, lane);
+    uint32_t mask = unit_mask<NT, DUR, RANGE>(R.d, sv, ev, R.tv, R.e0, n, dlo, dhi, A.start_s, A.end_s, bmi4,
                                                ns4, s_bm, lane);
     if (__ballot(mask != 0) == 0) return;
     if (A.unit_cap) mask = cap_unit_mask(mask, A.unit_cap, lane);
@@ -891,9 +900,9 @@ __global__ void __launch_bounds__(kResThreads, 1) search_resident_kernel(Residen
       const uint32_t blk = block_of(A.ubase, nsegs, ua + Rg.k, lane);
       const PoolBlk &P = A.blk[blk];
       const uint32_t n = rfl(P.nent), bmi4 = rfl(P.bmi4), ns4 = rfl(P.nsets4);
-      u32x4 ev[kSteps];
-      if (RANGE) unit_ends<NTL>(Rg.d, Rg.s, ev, uniform_ptr(P.scan), rfl(P.npad), Rg.e0, lane);
-      uint32_t mask = unit_mask<NT, DUR, RANGE>(Rg.d, Rg.s, ev, Rg.tv, Rg.e0, n, dlo, dhi, start_s, end_s, bmi4, ns4,
+      u32x4 sv[kSteps], ev[kSteps];
+      if (RANGE) unit_ends<NTL>(Rg.d, rfl(A.sbase[blk]), sv, ev, uniform_ptr(P.scan), rfl(P.npad), Rg.e0, lane);
+      uint32_t mask = unit_mask<NT, DUR, RANGE>(Rg.d, sv, ev, Rg.tv, Rg.e0, n, dlo, dhi, start_s, end_s, bmi4, ns4,
                                                  s_bm, lane);
       if (__ballot(mask != 0) == 0) return;
       if (ucap) mask = cap_unit_mask(mask, ucap, lane);

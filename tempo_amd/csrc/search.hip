@@ -2031,6 +2031,7 @@ void device_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>
       ns.scan = d.dur32;
       ns.ncol = d.narrow_base;
       ns.npad = uint32_t(d.npad);
+      ns.sbase = d.sbase;
       for (uint32_t t = 0; t < q.nterms && all_narrow; t++) {
         const size_t k = size_t(kidx[t]);
         if (d.narrow_slot.size() <= k || d.narrow_slot[k] < 0 || d.narrow_slot[k] > 255 || !b.narrow[k]) {

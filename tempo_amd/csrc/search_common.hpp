@@ -75,7 +75,7 @@ __device__ __forceinline__ const __attribute__((address_space(1))) T *G(const vo
   return (const __attribute__((address_space(1))) T *)(p);
 }
 
-// The pool kernels' compact duration column (devctx.hip, ds = D16 | span16 << 16): D16 =
+// The pool kernels' packed scan word (ds_word.hpp, ds = D16 | carry << 16 | rel start << 17): D16 =
 // 2 x whole ms + (a sub-ms remainder), saturated at 0xffff, is exact for duration bounds up
 // to this many ms (larger bounds take the other search paths)
 constexpr uint64_t kDs16MaxMs = 32767;
@@ -145,6 +145,7 @@ struct NarrowSeg {
   const uint32_t *scan;
   const uint8_t *ncol;
   uint32_t npad;
+  uint32_t sbase;  // the block's base second of its packed scan words (ds_word.hpp)
   std::array<uint8_t, kArgTerms> slot, nsets;
   std::array<const NarrowDict *, kArgTerms> dict;
 };
