@@ -392,7 +392,8 @@ int tsg_search_batch(tsg_ctx *ctx, const tsg_search_item *items, size_t n, uint3
  * device's CUs): search launches plan for n CUs. "xsplit" = 0/1: the resident kernel's
  * XCD-weighted split (default TSG_RES_XSPLIT, off). "lb_bitmap" = 0/1/2: full scans on the
  * dictionary-pass path return one bit per entry never / always / after a dense one (default
- * TSG_LB_BITMAP, 2). TSG_E_INVALID for an unknown name. */
+ * TSG_LB_BITMAP, 2). "proto_batch_jobs" = k: tsg_proto_search_batch launches cover at most k jobs
+ * (0 = the default, 4096). TSG_E_INVALID for an unknown name. */
 int tsg_debug_set(const char *name, int64_t value);
 
 /* Durations (ns) of the search kernels launched with TSG_SEARCH_TIME_DEFER since
@@ -565,6 +566,29 @@ int tsg_proto_block_info(const tsg_proto_block *b, uint64_t out[4]);
  * fails to decode, an index/page/object framing error, reached before the limit break. */
 int tsg_proto_search(tsg_ctx *ctx, tsg_proto_block *b, const tsg_proto_request *req, tsg_proto_result **out);
 void tsg_proto_result_free(tsg_proto_result *r);
+/* Many proto searches in one call (ABI 7): what a querier working through the frontend's
+ * "block B, pages [p, p+k), request R" jobs issues. Item i is one tsg_proto_search(ctx,
+ * items[i].block, items[i].req, &outs[i]): the same records in the same order, the same three
+ * metrics, the same status (free each result with tsg_proto_result_free). The items of one
+ * device are served under one hold of the device by one host-to-device copy (a job table and
+ * every item's term bitmaps), one kernel launch, one copy back and one synchronise (a launch
+ * covers at most 4096 jobs; a larger batch runs as consecutive launches); devices are handled in
+ * context order, one after another. kernel_ns of a result is the duration of the launch that
+ * served it, so the items of one launch share a value. Items may name the same block any
+ * number of times, and blocks on different devices. A failed item (TSG_E_CORRUPT as
+ * tsg_proto_search; TSG_E_UNSUPPORTED for more than 16 tags; TSG_E_INVALID for a block that is
+ * not resident) has outs[i] == NULL and its code in statuses[i] (optional) and does not disturb
+ * the others. Returns TSG_OK when every item succeeded, else the lowest-index failing item's
+ * status with that item's message in tsg_last_error (the rule of tsg_search_batch). n == 0
+ * returns TSG_OK. TSG_E_INVALID, before any work: ctx NULL, n > 0 with items or outs NULL, an
+ * item with a NULL block or req, or with ntags > 0 and a NULL tag array. Test hook:
+ * tsg_debug_set("proto_batch_jobs", k) lowers the jobs per launch to k (0 = the default). */
+typedef struct tsg_proto_item {
+  tsg_proto_block *block;
+  const tsg_proto_request *req;
+} tsg_proto_item;
+int tsg_proto_search_batch(tsg_ctx *ctx, const tsg_proto_item *items, size_t n, tsg_proto_result **outs,
+                           int32_t *statuses /* may be NULL */);
 
 /* Go strconv semantics used by matchAttributes (tooling / tests): kind 0 ParseInt(s, 10, 64)
  * -> *i, 1 ParseFloat(s, 64) -> *f, 2 ParseBool -> *i. Returns 1 when Go returns err == nil. */

@@ -2926,51 +2926,96 @@ int tsg_proto_block_info(const tsg_proto_block *b, uint64_t out[4]) {
   out[3] = b->b.device_bytes;
   return TSG_OK;
 }
+// A finished proto search as the caller's result: TraceSearchMetadata of the matched objects
+// from the block's host columns, the metrics, the launch's duration.
+static tsg_proto_result *proto_result_new(const ProtoBlock &pb, const ProtoOut &o) {
+  auto *h = new ProtoHolder();
+  std::unique_ptr<ProtoHolder> g(h);
+  for (uint32_t i : o.traces) {
+    h->id_off.push_back(uint32_t(h->ids.size()));
+    h->id_len.push_back(pb.id_len[i]);
+    h->ids.insert(h->ids.end(), pb.ids.begin() + pb.id_off[i], pb.ids.begin() + pb.id_off[i] + pb.id_len[i]);
+    h->svc.emplace_back(pb.names, pb.svc_off[i], pb.svc_len[i]);
+    h->root.emplace_back(pb.names, pb.root_off[i], pb.root_len[i]);
+    h->start.push_back(pb.start_ns[i]);
+    h->dur.push_back(pb.dur_ms[i]);
+    h->obj.push_back(i);
+  }
+  for (size_t i = 0; i < h->svc.size(); i++) {
+    h->svc_p.push_back(h->svc[i].c_str());
+    h->root_p.push_back(h->root[i].c_str());
+    h->svc_len.push_back(uint32_t(h->svc[i].size()));
+    h->root_len.push_back(uint32_t(h->root[i].size()));
+  }
+  tsg_proto_result &r = h->pub;
+  r.n = uint32_t(o.traces.size());
+  r.trace_ids = h->ids.data();
+  r.trace_id_off = h->id_off.data();
+  r.trace_id_len = h->id_len.data();
+  r.root_service_name = h->svc_p.data();
+  r.root_trace_name = h->root_p.data();
+  r.root_service_name_len = h->svc_len.data();
+  r.root_trace_name_len = h->root_len.data();
+  r.start_time_unix_nano = h->start.data();
+  r.duration_ms = h->dur.data();
+  r.object_idx = h->obj.data();
+  r.inspected_traces = o.inspected_traces;
+  r.inspected_bytes = o.inspected_bytes;
+  r.skipped_traces = o.skipped_traces;
+  r.kernel_ns = o.kernel_ns;
+  return &g.release()->pub;
+}
+static bool proto_request_ok(const tsg_proto_request *req) {
+  return req && (!req->ntags || (req->keys && req->key_lens && req->values && req->value_lens));
+}
 int tsg_proto_search(tsg_ctx *ctx, tsg_proto_block *b, const tsg_proto_request *req, tsg_proto_result **out) {
-  if (!ctx || !b || !req || !out || (req->ntags && (!req->keys || !req->key_lens || !req->values || !req->value_lens)))
-    return TSG_E_INVALID;
+  if (!ctx || !b || !out || !proto_request_ok(req)) return TSG_E_INVALID;
   *out = nullptr;
   return guard([&] {
     ProtoOut o;
     proto_search(b->b, *req, o);
     if (o.status != TSG_OK) fail(o.status, o.error);
-    auto *h = new ProtoHolder();
-    std::unique_ptr<ProtoHolder> g(h);
-    const ProtoBlock &pb = b->b;
-    for (uint32_t i : o.traces) {
-      h->id_off.push_back(uint32_t(h->ids.size()));
-      h->id_len.push_back(pb.id_len[i]);
-      h->ids.insert(h->ids.end(), pb.ids.begin() + pb.id_off[i], pb.ids.begin() + pb.id_off[i] + pb.id_len[i]);
-      h->svc.emplace_back(pb.names, pb.svc_off[i], pb.svc_len[i]);
-      h->root.emplace_back(pb.names, pb.root_off[i], pb.root_len[i]);
-      h->start.push_back(pb.start_ns[i]);
-      h->dur.push_back(pb.dur_ms[i]);
-      h->obj.push_back(i);
-    }
-    for (size_t i = 0; i < h->svc.size(); i++) {
-      h->svc_p.push_back(h->svc[i].c_str());
-      h->root_p.push_back(h->root[i].c_str());
-      h->svc_len.push_back(uint32_t(h->svc[i].size()));
-      h->root_len.push_back(uint32_t(h->root[i].size()));
-    }
-    tsg_proto_result &r = h->pub;
-    r.n = uint32_t(o.traces.size());
-    r.trace_ids = h->ids.data();
-    r.trace_id_off = h->id_off.data();
-    r.trace_id_len = h->id_len.data();
-    r.root_service_name = h->svc_p.data();
-    r.root_trace_name = h->root_p.data();
-    r.root_service_name_len = h->svc_len.data();
-    r.root_trace_name_len = h->root_len.data();
-    r.start_time_unix_nano = h->start.data();
-    r.duration_ms = h->dur.data();
-    r.object_idx = h->obj.data();
-    r.inspected_traces = o.inspected_traces;
-    r.inspected_bytes = o.inspected_bytes;
-    r.skipped_traces = o.skipped_traces;
-    r.kernel_ns = o.kernel_ns;
-    *out = &g.release()->pub;
+    *out = proto_result_new(b->b, o);
   });
+}
+int tsg_proto_search_batch(tsg_ctx *ctx, const tsg_proto_item *items, size_t n, tsg_proto_result **outs,
+                           int32_t *statuses) {
+  if (!ctx || (n && (!items || !outs))) return TSG_E_INVALID;
+  for (size_t i = 0; i < n; i++)
+    if (!items[i].block || !proto_request_ok(items[i].req)) return TSG_E_INVALID;
+  for (size_t i = 0; i < n; i++) {
+    outs[i] = nullptr;
+    if (statuses) statuses[i] = TSG_OK;
+  }
+  if (!n) return TSG_OK;
+  std::vector<ProtoOut> o;
+  const int rc = guard([&] {
+    if (!proto_search_batch) fail(TSG_E_DEVICE, "tsg_proto_search_batch: this build of the library has no device half");
+    std::vector<ProtoItem> it(n);
+    for (size_t i = 0; i < n; i++) it[i] = ProtoItem{&items[i].block->b, items[i].req};
+    o.resize(n);
+    proto_search_batch(ctx->c, it.data(), n, o.data());
+  });
+  if (rc) {
+    if (statuses) std::fill(statuses, statuses + n, int32_t(rc));
+    return rc;
+  }
+  int first = TSG_OK;
+  std::string first_msg;
+  for (size_t i = 0; i < n; i++) {
+    int st = o[i].status;
+    if (st == TSG_OK) {
+      st = guard([&] { outs[i] = proto_result_new(items[i].block->b, o[i]); });
+      if (st) o[i].error = tsg_last_error();
+    }
+    if (statuses) statuses[i] = st;
+    if (st && !first) {
+      first = st;
+      first_msg = o[i].error;
+    }
+  }
+  if (first) set_last_error(first_msg);
+  return first;
 }
 void tsg_proto_result_free(tsg_proto_result *r) { delete reinterpret_cast<ProtoHolder *>(r); }
 

@@ -123,7 +123,7 @@ void ctx_shutdown(Ctx &c) {
     for (DevBuf *b : {&dc->desc, &dc->vmatch, &dc->bitmaps, &dc->gran, &dc->ticket, &dc->out, &dc->regions,
                       &dc->seg_counts, &dc->hdr, &dc->err, &dc->maskbits, &dc->agg, &dc->stamps, &dc->gbm, &dc->lkhits,
                       &dc->done, &dc->steal, &dc->fpages, &dc->fhits, &dc->fres, &dc->farena, &dc->fcrc, &dc->fdst, &dc->foff,
-                      &dc->danyf, &dc->pool_head, &dc->lkslab, &dc->lkslabdesc, &dc->pbm, &dc->pout})
+                      &dc->danyf, &dc->pool_head, &dc->lkslab, &dc->lkslabdesc, &dc->pbm, &dc->pout, &dc->pjob})
       b->release();
     for (hipEvent_t e : dc->tring) (void)hipEventDestroy(e);
     dc->hdesc.release();

@@ -99,6 +99,7 @@ struct DeviceCtx {
   DevBuf maskbits, agg, stamps, gbm, lkhits;
   DevBuf lkslab, lkslabdesc;  // lookup: transposed bloom slabs + their member tables
   DevBuf pbm, pout;  // proto search: term bitmaps, per-object match/error bits
+  DevBuf pjob;       // batched proto search: [job table | first-workgroup prefix | term bitmaps]
   DevBuf fpages, fhits, fres, farena, fcrc, fdst, foff;  // device findOne (find.hip)
   HostBuf hdesc, hout;
   // lookup: pinned staging of the caller's (pageable) probe ids, two chunks in turn: the host

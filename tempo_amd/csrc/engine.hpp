@@ -265,6 +265,7 @@ uint64_t resident_batch_end(DeviceCtx &dc, uint64_t launches_before);
 // (0/1: the resident kernel's XCD-weighted split; default TSG_RES_XSPLIT, 0)
 int debug_set(const char *name, int64_t value);
 void find_zstd_lane(bool on);  // find.hip ("zstd_find_lane": 1 = the one-lane zstd page decoder)
+void proto_batch_cap(uint32_t k);  // proto_scan.hip ("proto_batch_jobs": jobs per batched launch, 0 = the default)
 uint32_t debug_groups();
 uint32_t debug_lb_bitmap();  // "lb_bitmap": 0 never / 1 always / 2 auto (TSG_LB_BITMAP, default 2)
 bool debug_xsplit();

@@ -411,6 +411,10 @@ int debug_set(const char *name, int64_t value) {
     find_zstd_lane(value != 0);
     return TSG_OK;
   }
+  if (!std::strcmp(name, "proto_batch_jobs")) {  // (proto_scan.hip: jobs per batched launch, 0 = default)
+    proto_batch_cap(uint32_t(std::min<int64_t>(1 << 30, std::max<int64_t>(0, value))));
+    return TSG_OK;
+  }
   if (!std::strcmp(name, "lb_bitmap")) {
     g_lb_bitmap.store(uint32_t(std::min<int64_t>(2, std::max<int64_t>(0, value))));
     return TSG_OK;

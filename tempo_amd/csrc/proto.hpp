@@ -77,6 +77,16 @@ struct ProtoOut {
   uint64_t kernel_ns = 0;
 };
 void proto_search(ProtoBlock &b, const tsg_proto_request &req, ProtoOut &out);
+// tsg_proto_search_batch's device half (proto_scan.hip): outs[i] is what proto_search gives for
+// items[i], computed by one launch per device (consecutive launches past the job cap). A
+// failing item has its code and message in outs[i].status / .error; nothing is thrown for it.
+// Weak: a host-only build of the library (the sanitizer stand-in for the device) links
+// without it, and the batch then reports TSG_E_DEVICE.
+struct ProtoItem {
+  ProtoBlock *b;
+  const tsg_proto_request *req;
+};
+void proto_search_batch(Ctx &c, const ProtoItem *items, size_t n, ProtoOut *outs) __attribute__((weak));
 
 // Go strconv semantics used by matchAttributes (exposed for the tests through the ABI)
 bool go_parse_int(std::string_view s, int64_t &out);

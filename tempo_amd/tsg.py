@@ -148,6 +148,10 @@ class _ProtoResult(C.Structure):
                 ("root_trace_name_len", C.POINTER(C.c_uint32))]
 
 
+class _ProtoItem(C.Structure):
+    _fields_ = [("block", C.c_void_p), ("req", C.c_void_p)]
+
+
 class _LookupResult(C.Structure):
     _fields_ = [("n", C.c_uint64), ("id_idx", C.POINTER(C.c_uint32)), ("block_idx", C.POINTER(C.c_uint32)),
                 ("record_idx", C.POINTER(C.c_int32)), ("record_start", C.POINTER(C.c_uint64)),
@@ -168,7 +172,7 @@ EXPORTED = [
     "tsg_block_tag_values", "tsg_free", "tsg_search", "tsg_result_free", "tsg_kernel_times", "tsg_results_combine",
     "tsg_v2block_open", "tsg_v2block_close", "tsg_lookup_ids", "tsg_lookup_result_free", "tsg_find_ids",
     "tsg_find_result_free", "tsg_proto_block_open", "tsg_proto_block_close", "tsg_proto_block_info",
-    "tsg_proto_search", "tsg_proto_result_free", "tsg_go_parse", "tsg_write_v2_block", "tsg_write_v2_block_pages",
+    "tsg_proto_search", "tsg_proto_search_batch", "tsg_proto_result_free", "tsg_go_parse", "tsg_write_v2_block", "tsg_write_v2_block_pages",
     "tsg_write_search_block", "tsg_write_wal_search", "tsg_fb_search_entry", "tsg_fb_search_header", "tsg_synth_search_block",
     "tsg_synth_v2_block", "tsg_live_block_open_mem", "tsg_search_tags", "tsg_search_tag_values",
     "tsg_result_pack", "tsg_wire_merge", "tsg_search_batch", "tsg_debug_set",
@@ -246,6 +250,8 @@ def lib():
         L.tsg_proto_block_close.argtypes = [vp]
         L.tsg_proto_block_info.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.tsg_proto_search.argtypes = [vp, vp, C.POINTER(_ProtoRequest), C.POINTER(C.POINTER(_ProtoResult))]
+        L.tsg_proto_search_batch.argtypes = [vp, C.POINTER(_ProtoItem), C.c_size_t,
+                                             C.POINTER(C.POINTER(_ProtoResult)), C.POINTER(C.c_int32)]
         L.tsg_proto_result_free.argtypes = [C.POINTER(_ProtoResult)]
         L.tsg_go_parse.argtypes = [C.c_int, C.c_char_p, C.c_size_t, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
         L.tsg_write_v2_block_pages.argtypes = [C.c_char_p, vp, C.c_char_p, C.POINTER(C.c_uint64), C.c_size_t,
@@ -825,14 +831,15 @@ class Engine:
     def open_proto_block(self, path: str, device: int = 0) -> "ProtoBlock":
         return ProtoBlock(self, path, device)
 
-    def proto_search(self, block: "ProtoBlock", tags: Optional[dict] = None, min_ms: int = 0,
-                     max_ms: int = 0, start: int = 0, end: int = 0, limit: int = 20,
-                     start_page: int = 0, total_pages: int = 0, max_bytes: int = 0,
-                     chunk_size_bytes: int = 0) -> ProtoSearchResponse:
-        """v2.BackendBlock.Search of one block (tsg_proto_search); raises TsgError where the
-        reference's Search returns an error."""
+    @staticmethod
+    def _proto_request(tags=None, min_ms: int = 0, max_ms: int = 0, start: int = 0, end: int = 0,
+                       limit: int = 20, start_page: int = 0, total_pages: int = 0, max_bytes: int = 0,
+                       chunk_size_bytes: int = 0):
+        """(tsg_proto_request, the arrays it points into). tags: a dict, or a sequence of (key,
+        value) pairs (SearchRequest.Tags is a map: a repeated key keeps its last value)."""
+        pairs = tags.items() if hasattr(tags, "items") else (tags or ())
         items = [(k.encode() if isinstance(k, str) else k, v.encode() if isinstance(v, str) else v)
-                 for k, v in (tags or {}).items()]
+                 for k, v in pairs]
         n = len(items)
         keys = (C.c_char_p * max(n, 1))(*[k for k, _ in items])
         vals = (C.c_char_p * max(n, 1))(*[v for _, v in items])
@@ -840,8 +847,11 @@ class Engine:
         vl = (C.c_uint32 * max(n, 1))(*[len(v) for _, v in items])
         req = _ProtoRequest(n, keys, kl, vals, vl, min_ms, max_ms, start, end, limit, start_page,
                             total_pages, max_bytes, chunk_size_bytes)
-        rp = C.POINTER(_ProtoResult)()
-        _check(lib().tsg_proto_search(self.h, block.h, C.byref(req), C.byref(rp)))
+        return req, (keys, vals, kl, vl)
+
+    @staticmethod
+    def _proto_response(rp) -> ProtoSearchResponse:
+        """A tsg_proto_result as a ProtoSearchResponse; frees the result."""
         try:
             r = rp.contents
             traces, objs = [], []
@@ -860,6 +870,44 @@ class Engine:
                                        r.kernel_ns)
         finally:
             lib().tsg_proto_result_free(rp)
+
+    def proto_search(self, block: "ProtoBlock", tags: Optional[dict] = None, min_ms: int = 0,
+                     max_ms: int = 0, start: int = 0, end: int = 0, limit: int = 20,
+                     start_page: int = 0, total_pages: int = 0, max_bytes: int = 0,
+                     chunk_size_bytes: int = 0) -> ProtoSearchResponse:
+        """v2.BackendBlock.Search of one block (tsg_proto_search); raises TsgError where the
+        reference's Search returns an error."""
+        req, _keep = self._proto_request(tags, min_ms, max_ms, start, end, limit, start_page, total_pages,
+                                         max_bytes, chunk_size_bytes)
+        rp = C.POINTER(_ProtoResult)()
+        _check(lib().tsg_proto_search(self.h, block.h, C.byref(req), C.byref(rp)))
+        return self._proto_response(rp)
+
+    def proto_search_batch(self, items, raw: bool = False):
+        """tsg_proto_search_batch: items is a list of (ProtoBlock, dict) pairs, each dict the
+        keyword arguments of proto_search. One launch per device serves them all. Returns a
+        list with, per item, the ProtoSearchResponse proto_search returns or the TsgError it
+        would raise (per-item failures do not raise). raw: (that list, the call's return code)."""
+        n = len(items)
+        reqs = [self._proto_request(**kw) for _, kw in items]
+        arr = (_ProtoItem * max(n, 1))()
+        for i, (blk, _) in enumerate(items):
+            arr[i].block = blk.h
+            arr[i].req = C.addressof(reqs[i][0])
+        outs = (C.POINTER(_ProtoResult) * max(n, 1))()
+        sts = (C.c_int32 * max(n, 1))()
+        rc = lib().tsg_proto_search_batch(self.h, arr, n, outs, sts)
+        msg = lib().tsg_last_error().decode(errors="replace") if rc != TSG_OK else ""
+        if rc != TSG_OK and all(sts[i] == TSG_OK for i in range(n)):
+            raise TsgError(rc, msg)  # (the whole call was refused: no item ran)
+        res, first = [], True
+        for i in range(n):
+            if sts[i] == TSG_OK:
+                res.append(self._proto_response(outs[i]))
+                continue
+            res.append(TsgError(sts[i], msg if first else f"batch item {i} failed"))
+            first = False
+        return (res, rc) if raw else res
 
     def close(self):
         self._raw_calls = {}
