@@ -393,8 +393,16 @@ int tsg_search_batch(tsg_ctx *ctx, const tsg_search_item *items, size_t n, uint3
  * XCD-weighted split (default TSG_RES_XSPLIT, off). "lb_bitmap" = 0/1/2: full scans on the
  * dictionary-pass path return one bit per entry never / always / after a dense one (default
  * TSG_LB_BITMAP, 2). "proto_batch_jobs" = k: tsg_proto_search_batch launches cover at most k jobs
- * (0 = the default, 4096). TSG_E_INVALID for an unknown name. */
+ * (0 = the default, 4096). "dict_stream_min" = b: a key's dictionary of more than b bytes is
+ * matched as one byte stream (0 = the default, 1 MiB); a query with a term that streams only
+ * because of the hook takes the dictionary-pass path. "dict_stream_span" = b: every wave of the
+ * stream kernel owns b bytes, a multiple of 1024 from 1024 to 65536 (0 = the planned span;
+ * TSG_E_INVALID for another value). TSG_E_INVALID for an unknown name.
+ * tsg_debug_get reads a process-wide counter: "dict_stream_jobs" / "dict_lane_jobs" = the
+ * (block, term) dictionary jobs of dictionary-pass searches that the stream kernel / the
+ * lane-per-value kernel ran so far. TSG_E_INVALID for an unknown name or a NULL out. */
 int tsg_debug_set(const char *name, int64_t value);
+int tsg_debug_get(const char *name, uint64_t *out);
 
 /* Durations (ns) of the search kernels launched with TSG_SEARCH_TIME_DEFER since
  * the last call, in launch order per device (devices in context order). Waits for

@@ -691,6 +691,7 @@ static void wal_refresh_common(tsg_ctx *ctx, const tsg_block *old, const uint8_t
 }  // namespace tsg
 
 using namespace tsg;
+std::atomic<uint64_t> tsg::g_dict_stream_jobs{0}, tsg::g_dict_lane_jobs{0};  // (tsg_debug_get)
 
 extern "C" {
 
@@ -2625,6 +2626,13 @@ int tsg_debug_set(const char *name, int64_t value) {
     return TSG_OK;
   }
   return debug_set(name, value);
+}
+int tsg_debug_get(const char *name, uint64_t *out) {
+  if (!name || !out) return TSG_E_INVALID;
+  if (!std::strcmp(name, "dict_stream_jobs")) *out = g_dict_stream_jobs.load();
+  else if (!std::strcmp(name, "dict_lane_jobs")) *out = g_dict_lane_jobs.load();
+  else return TSG_E_INVALID;
+  return TSG_OK;
 }
 
 int tsg_kernel_times(tsg_ctx *ctx, uint64_t *ns, size_t cap, size_t *n) {

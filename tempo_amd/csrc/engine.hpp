@@ -1,6 +1,7 @@
 // engine.hpp — device side of libtsg: per-device context, resident blocks and the
 // search / lookup pipelines. The kernels live in engine.hip.
 #pragma once
+#include <atomic>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -266,6 +267,13 @@ uint64_t resident_batch_end(DeviceCtx &dc, uint64_t launches_before);
 int debug_set(const char *name, int64_t value);
 void find_zstd_lane(bool on);  // find.hip ("zstd_find_lane": 1 = the one-lane zstd page decoder)
 void proto_batch_cap(uint32_t k);  // proto_scan.hip ("proto_batch_jobs": jobs per batched launch, 0 = the default)
+// search.hip: "dict_stream_min" (dictionaries above this many bytes stream; 0 = 1 MiB) and
+// "dict_stream_span" (bytes per wave; false unless 0 or a multiple of 1024 up to 64 KiB)
+void dict_stream_min(uint64_t bytes);
+bool dict_stream_span(uint64_t bytes);
+// tsg_debug_get "dict_stream_jobs" / "dict_lane_jobs" (capi.cpp; counted in search.hip): the dictionary
+// jobs of general-path searches that dict_stream_kernel / prep_kernel's lane-per-value path ran
+extern std::atomic<uint64_t> g_dict_stream_jobs, g_dict_lane_jobs;
 uint32_t debug_groups();
 uint32_t debug_lb_bitmap();  // "lb_bitmap": 0 never / 1 always / 2 auto (TSG_LB_BITMAP, default 2)
 bool debug_xsplit();

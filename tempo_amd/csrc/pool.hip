@@ -419,6 +419,12 @@ int debug_set(const char *name, int64_t value) {
     g_lb_bitmap.store(uint32_t(std::min<int64_t>(2, std::max<int64_t>(0, value))));
     return TSG_OK;
   }
+  if (!std::strcmp(name, "dict_stream_min")) {  // (search.hip: dictionaries above this many bytes stream, 0 = 1 MiB)
+    dict_stream_min(uint64_t(std::max<int64_t>(0, value)));
+    return TSG_OK;
+  }
+  if (!std::strcmp(name, "dict_stream_span"))  // (search.hip: bytes per wave, a multiple of 1024 up to 64 KiB, 0 = planned)
+    return value >= 0 && dict_stream_span(uint64_t(value)) ? TSG_OK : TSG_E_INVALID;
   return TSG_E_INVALID;
 }
 

@@ -265,6 +265,17 @@ struct StreamJob {
 };
 static_assert(sizeof(StreamJob) == 64, "StreamJob layout");
 constexpr uint32_t kStreamPairMax = 11;  // its bytes of a lane's 16 starts lie in this lane's + the next lane's 16
+// test hooks (tsg_debug_set): "dict_stream_min" replaces kStreamMinBytes (0 = 1 MiB), so that a
+// dictionary of a few KiB streams; "dict_stream_span" forces the span (0 = the planned one).
+// (g_dict_stream_jobs / g_dict_lane_jobs, engine.hpp: the jobs each path ran, for tsg_debug_get)
+static std::atomic<uint64_t> g_stream_min{0};
+static std::atomic<uint32_t> g_stream_span{0};
+void dict_stream_min(uint64_t bytes) { g_stream_min.store(bytes); }
+bool dict_stream_span(uint64_t bytes) {
+  if (bytes && (bytes % 1024 != 0 || bytes > kStreamSpan)) return false;
+  g_stream_span.store(uint32_t(bytes));
+  return true;
+}
 
 // bit 7 of each byte of the result: that byte of x is non-zero (exact, no carries across bytes)
 __device__ __forceinline__ uint32_t nz_bytes(uint32_t x) { return (((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x) & 0x80808080u; }
@@ -1904,6 +1915,10 @@ void device_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>
   seg_desc.clear();
   nsegv.clear();
   bool all_narrow = q.nterms <= uint32_t(kArgTerms);
+  // the "dict_stream_min" test hook: a dictionary it lets stream is small enough for the one-launch
+  // paths, which match dictionaries themselves; such a query takes the general path instead
+  const uint64_t hook_min = g_stream_min.load(), stream_min = hook_min ? hook_min : kStreamMinBytes;
+  bool hooked_stream = false;
   uint32_t fast_stage = 0, fast_bm = 0, fast_bm8 = 0, fast_vbits = 0, fast_words = 1, fast_self = 0;
   for (size_t bi_ = 0; bi_ < blocks.size(); bi_++) {
     const auto &bp = blocks[bi_];
@@ -1960,8 +1975,9 @@ void device_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>
       jb.item_base = items;
       // a large dictionary of values >= 16 B on average: one byte-stream pass
       // (dict_stream_kernel) instead of a lane per value
-      const bool stream = dc.dict_stream && k.dict_nbytes > kStreamMinBytes && q.value_lens[t] >= 2 &&
+      const bool stream = dc.dict_stream && k.dict_nbytes > stream_min && q.value_lens[t] >= 2 &&
                           q.value_lens[t] <= kStreamMaxNeedle && k.dict_nbytes >= 16ull * k.nvals;
+      hooked_stream = hooked_stream || (stream && k.dict_nbytes <= kStreamMinBytes);
       if (!stream) items += uint32_t(align_up(std::max<uint32_t>(k.nvals, 1), 64));
       const uint32_t words = (k.nsets + 31) / 32;
       bm_total += words + 2;  // +2: a wave's ballot writes whole 64-value word pairs
@@ -2134,7 +2150,7 @@ void device_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>
         nbms.push_back(bm);
       }
   }
-  const bool fast = !dc.fast_off && nsegs <= uint32_t(kArgSegs) && q.nterms <= 4 && needles.size() <= size_t(kArgNeedle) &&
+  const bool fast = !dc.fast_off && !hooked_stream && nsegs <= uint32_t(kArgSegs) && q.nterms <= 4 && needles.size() <= size_t(kArgNeedle) &&
                     (fast_stage <= kFastStageWords || narrow);
   // workgroups: about one resident wave of them (occupancy x CUs), each owning a
   // contiguous tile range of one block
@@ -2381,6 +2397,7 @@ void device_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>
       for (const auto &sj : stream_jobs) tot += sj.lead + sj.nbytes;
       uint64_t sp = tot / (uint64_t(std::max(dc.num_cu, 1)) * 16);
       sp = std::min<uint64_t>(kStreamSpan, std::max<uint64_t>(8192, (sp + 1023) / 1024 * 1024));
+      if (const uint32_t hook_span = g_stream_span.load()) sp = hook_span;  // ("dict_stream_span")
       stream_span = uint32_t(sp);
       stream_waves = 0;
       for (auto &sj : stream_jobs) {
@@ -2425,6 +2442,8 @@ void device_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>
         src, dd, uint32_t(total_desc / 16), uint32_t(o_jobs), uint32_t(o_jb), uint32_t(jobs.size()), items,
         uint32_t(o_nd), uint32_t(needles.size()), static_cast<uint8_t *>(dc.vmatch.p),
         static_cast<uint32_t *>(dc.bitmaps.p), anyf);
+    g_dict_lane_jobs.fetch_add(jobs.size() - stream_jobs.size(), std::memory_order_relaxed);
+    g_dict_stream_jobs.fetch_add(stream_jobs.size(), std::memory_order_relaxed);
     if (!stream_jobs.empty())
       dict_stream_kernel<<<(stream_waves + kStreamWg - 1) / kStreamWg, 64 * kStreamWg, 0, s>>>(
           reinterpret_cast<const StreamJob *>(dd + o_stj), uint32_t(stream_jobs.size()), dd + o_nd,

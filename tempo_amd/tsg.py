@@ -175,7 +175,7 @@ EXPORTED = [
     "tsg_proto_search", "tsg_proto_search_batch", "tsg_proto_result_free", "tsg_go_parse", "tsg_write_v2_block", "tsg_write_v2_block_pages",
     "tsg_write_search_block", "tsg_write_wal_search", "tsg_fb_search_entry", "tsg_fb_search_header", "tsg_synth_search_block",
     "tsg_synth_v2_block", "tsg_live_block_open_mem", "tsg_search_tags", "tsg_search_tag_values",
-    "tsg_result_pack", "tsg_wire_merge", "tsg_search_batch", "tsg_debug_set",
+    "tsg_result_pack", "tsg_wire_merge", "tsg_search_batch", "tsg_debug_set", "tsg_debug_get",
     "tsg_shm_open", "tsg_shm_close", "tsg_shm_put", "tsg_shm_merge",
 ]
 
@@ -231,6 +231,7 @@ def lib():
         L.tsg_search_batch.argtypes = [vp, C.POINTER(_SearchItem), C.c_size_t, C.c_uint32,
                                        C.POINTER(C.POINTER(_Result)), C.POINTER(C.c_uint64)]
         L.tsg_debug_set.argtypes = [C.c_char_p, C.c_int64]
+        L.tsg_debug_get.argtypes = [C.c_char_p, C.POINTER(C.c_uint64)]
         L.tsg_shm_open.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(vp)]
         L.tsg_shm_close.argtypes = [vp]
         L.tsg_shm_put.argtypes = [vp, C.c_uint32, vp, C.c_size_t, C.c_double]
@@ -932,6 +933,14 @@ def debug_set(name: str, value: int) -> None:
     one-lane zstd page decoder of find; "lz4_writer_flags": checksum bits of the lz4 page
     writer, include/tsg.h)."""
     _check(lib().tsg_debug_set(name.encode(), value))
+
+
+def debug_get(name: str) -> int:
+    """tsg_debug_get: a process-wide counter ("dict_stream_jobs" / "dict_lane_jobs": dictionary jobs
+    the stream kernel / the lane-per-value kernel ran so far, include/tsg.h)."""
+    out = C.c_uint64(0)
+    _check(lib().tsg_debug_get(name.encode(), C.byref(out)))
+    return out.value
 
 
 def _seen(opts, seen):
