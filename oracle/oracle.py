@@ -288,14 +288,19 @@ class V2Block:
         assert rc == 0, rc
         return i.value, s.value, l.value
 
-    def find(self, tid):
+    def find(self, tid, status=False):
+        """The object, or None when findOne finds nothing. status=True: (rc, object), where rc is the
+        error findOne returns for this id (ORC_CORRUPT: a damaged page before the id was found);
+        without it an error is an AssertionError."""
         p, n = C.POINTER(C.c_uint8)(), C.c_size_t()
         rc = lib().orc_v2_find(self.h, tid, len(tid), C.byref(p), C.byref(n))
+        b = None
+        if p:
+            b = C.string_at(p, n.value)
+            lib().orc_free(p)
+        if status:
+            return rc, b
         assert rc == 0, rc
-        if not p:
-            return None
-        b = C.string_at(p, n.value)
-        lib().orc_free(p)
         return b
 
     def __del__(self):

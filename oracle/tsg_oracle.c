@@ -836,6 +836,37 @@ static int unmarshal_advance(const uint8_t **buf, size_t *len, const uint8_t **i
   return 0;
 }
 
+/* object.UnmarshalObjectFromReader (object.go:50-80) over a bytes.Reader holding buf[0 .. len):
+ * what findOne's iterator calls (iterator.go:30-32, finder_paged.go:89). Not the function above:
+ * the page's end differs. binary.Read is io.ReadFull of 4 bytes (encoding/binary, io.ReadAtLeast):
+ * io.EOF with nothing left, io.ErrUnexpectedEOF with 1..3 left. The id and object are one
+ * r.Read(b), len(b) = total - 8 as a uint32: bytes.Reader.Read answers io.EOF whenever the reader
+ * is at its end (also for an empty b), else copies what is left without an error, and a short
+ * count is the "read %d but expected %d" error (:69-71). Returns 1 for io.EOF (the iterator's
+ * clean end), < 0 for any other error. */
+static int unmarshal_from_reader(const uint8_t **buf, size_t *len, const uint8_t **id, uint32_t *idl,
+                                 const uint8_t **obj, size_t *objl) {
+  for (int field = 0; field < 2; field++) { /* totalLength (:52), idLength (:58) */
+    const size_t left = *len - 4u * (size_t)field;
+    if (left == 0) return 1;
+    if (left < 4) return -ORC_CORRUPT;
+  }
+  const uint32_t total = le32(*buf), il = le32(*buf + 4);
+  const uint8_t *b = *buf + 8;
+  const size_t bl = *len - 8;
+  const uint32_t rest = total - 8; /* (:63, wraps below 8 as the uint32 does) */
+  if (bl == 0) return 1;           /* r.Read at the reader's end (:65-68) */
+  if ((uint64_t)bl < rest) return -ORC_CORRUPT; /* short read (:69-71) */
+  if (il > rest) return -ORC_CORRUPT;           /* id length outside the buffer (:72-74) */
+  *id = b;
+  *idl = il;
+  *obj = b + il;
+  *objl = rest - il;
+  *buf = b + rest;
+  *len = bl - rest;
+  return 0;
+}
+
 /* ------------------------------------------------------------------------- */
 /* backend search block                                                        */
 struct orc_block {
@@ -1475,10 +1506,10 @@ int orc_v2_find(const orc_v2block *b, const uint8_t *id, size_t idl, uint8_t **o
   const uint8_t *cur = page, *oid, *obj;
   size_t cl = pl, objl;
   uint32_t oidl;
-  for (;;) {
-    int u = unmarshal_advance(&cur, &cl, &oid, &oidl, &obj, &objl);
-    if (u == 1) break;
-    if (u < 0) { rc = -u; break; }
+  for (;;) { /* iter.Next over bytes.NewReader(pages[0]) (finder_paged.go:89-108) */
+    int u = unmarshal_from_reader(&cur, &cl, &oid, &oidl, &obj, &objl);
+    if (u == 1) break;             /* io.EOF: nil, nil */
+    if (u < 0) { rc = -u; break; } /* nil, err: only an id not found before it gets here */
     if (oidl == idl && memcmp(oid, id, idl) == 0) {
       *out = (uint8_t *)malloc(objl ? objl : 1);
       memcpy(*out, obj, objl);

@@ -133,7 +133,9 @@ int orc_v2_bloom_test(const orc_v2block *b, const uint8_t *id, size_t idlen);
 /* indexReader.Find: record index (or -1), record fields */
 int orc_v2_index_find(const orc_v2block *b, const uint8_t *id, size_t idlen, int64_t *rec_idx,
                       uint64_t *start, uint32_t *length);
-/* BackendBlock.find: object bytes (malloc'd) or *out=NULL when absent */
+/* BackendBlock.find: object bytes (malloc'd) or *out=NULL when absent; the page's objects are read
+ * as findOne reads them (UnmarshalObjectFromReader over a bytes.Reader); an error of the page
+ * (ORC_CORRUPT) is returned for an id not found before it, with *out=NULL */
 int orc_v2_find(const orc_v2block *b, const uint8_t *id, size_t idlen, uint8_t **out,
                 size_t *out_len);
 /* includeBlock (tempodb.go:492-511); time window both 0 = off; range NULL = off */

@@ -5,7 +5,7 @@
 //   findOne                        tempodb/encoding/v2/finder_paged.go:79-110
 //   dataReader.Read (one record)   tempodb/encoding/v2/data_reader.go:45-125
 //   page framing                   tempodb/encoding/v2/page.go:28-57
-//   object framing / iterator      tempodb/encoding/v2/object.go:82-113, iterator.go
+//   object framing / iterator      tempodb/encoding/v2/object.go:50-80 (the reader form), iterator.go
 //   snappy framed stream           vendor/github.com/golang/snappy/decode.go:121-232, snappy_dev.hpp;
 //                                  block format decode_other.go:41-102
 //   lz4 frame (lz4-64k .. lz4)     vendor/github.com/pierrec/lz4/v4/reader.go, lz4_dev.hpp
