@@ -893,6 +893,7 @@ bool pool_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>> 
       b.col[t] = ns.ncol + uint64_t(ns.slot[t]) * ns.npad;
       b.bmi4 |= uint32_t(nbmi[i][t]) << (8 * t);
       b.nsets4 |= uint32_t(ns.nsets[t]) << (8 * t);
+      PA.bm_ns[nbmi[i][t]] = ns.nsets[t];  // (a slot is one (dictionary, term) pair: its blocks agree)
     }
     b.npad = ns.npad;
     b.nent = uint32_t(segs[i].n);

@@ -79,6 +79,9 @@ struct PoolArgs {
   uint32_t xsplit;
   unsigned long long *qstamps;       // resident kernel, timed queries: per workgroup {seen, end} (100 MHz)
   uint32_t xn[8], xr[8];
+  // the set count of each bitmap slot's (dictionary, term) pair: what the slot's byte table folds in
+  // (the planner gives a slot to one pair, so its blocks agree on it)
+  uint8_t bm_ns[kArgBms];
 };
 static_assert(sizeof(PoolArgs) <= 4096, "kernel arguments");
 
@@ -213,40 +216,119 @@ __device__ __forceinline__ uint32_t cap_unit_mask(uint32_t mask, uint32_t cap, i
 // The predicates of one unit (8 entries per lane) as a 32-bit lane mask, branch-free: every
 // test is evaluated for every entry and combined with bitwise ands (short-circuit tests
 // compiled to ~130 exec-mask branches per unit; with real, mixed values the lanes diverge
-// and the 150 MB scan ran 8 us longer than with uniform data, profiles/r03_launch).
-// ds: the packed scan word column (ds_word.hpp), sv / ev: start / end seconds (unit_ends);
-// lo/hi: the duration bounds in ds's units (0 / 2^32-1 when a side is absent); bm: the LDS
-// bitmaps.
-template <int NT, bool DUR, bool RANGE>
-__device__ __forceinline__ uint32_t unit_mask(const u32x4 (&d)[kSteps], const u32x4 (&sv4)[kSteps],
-                                              const u32x4 (&ev4)[kSteps], const uint32_t (&tv)[NT > 0 ? NT : 1][kSteps],
-                                              uint32_t e0, uint32_t n, uint32_t lo, uint32_t hi, uint32_t start_s,
-                                              uint32_t end_s, uint32_t bmi4, uint32_t ns4, const uint32_t *s_bm,
-                                              int lane) {
+// and the 150 MB scan ran 8 us longer than with uniform data, profiles/r03_launch). The tests
+// are ds_word.hpp's short forms, their wave-uniform parts in UnitPred (per query and block):
+// a term is one byte read of its LDS table, the duration one compare, the range two compares on
+// the packed word (each entry's verdict still costs a select and an or on its way into the mask).
+// The entries that do not exist (a block's last unit) are cut once per unit.
+//
+// Range, escapes: for a lane's four entries of a step where some start lies outside the 15-bit
+// window (rel 0x7fff) or some duration code is saturated (0xffff: durations from 32.768 s, ends
+// before the start, e.g. the end = 0 entries of pitfall P1), and for every entry of a block
+// whose base is too late for the word's thresholds (DsRange::fast), the word's tests are passed over and
+// the four range verdicts come from ds_word.hpp's decode: starts from the exact start column
+// where a start escaped, ends from the exact end column where an end did (rare; only the lanes
+// that need them load: a unit-wide reload moved 16 MB more per config-2 query, the PMC count in
+// profiles/r04_final). That decode sits under a per-lane branch, as the reloads always did: only
+// the lanes that need it run it, the others wait for them (not a wave-uniform branch; with 0.1 %
+// of the entries escaped about a fifth of a wave's steps take it).
+template <int NT>
+struct UnitPred {
+  DsDur dur;
+  DsRange rng;
+  uint32_t start_s, end_s, sbase, n;
+  uint32_t tb[NT > 0 ? NT : 1];  // each term's table in s_tb (bytes)
+};
+template <int NT>
+__device__ __forceinline__ UnitPred<NT> unit_pred(uint32_t dlo, uint32_t dhi, uint32_t start_s, uint32_t end_s,
+                                                  uint32_t sbase, uint32_t n, uint32_t bmi4) {
+  UnitPred<NT> P;
+  P.dur = ds_dur_form(dlo, dhi);
+  P.rng = ds_range_form(sbase, start_s, end_s);
+  P.start_s = start_s;
+  P.end_s = end_s;
+  P.sbase = sbase;
+  P.n = n;
+#pragma unroll
+  for (int q = 0; q < (NT > 0 ? NT : 1); q++) P.tb[q] = ((bmi4 >> (8 * q)) & 0xffu) * 256u;
+  return P;
+}
+template <int NT, bool DUR, bool RANGE, bool NTL>
+__device__ __forceinline__ uint32_t unit_mask(const UnitRegs<NT> &R, const UnitPred<NT> &P, const uint8_t *s_tb,
+                                              const uint32_t *scan, uint32_t npad, int lane) {
   uint32_t mask = 0;
 #pragma unroll
-  for (int k = 0; k < kSteps; k++) {
-    const uint32_t dv[4] = {d[k].x & 0xffffu, d[k].y & 0xffffu, d[k].z & 0xffffu, d[k].w & 0xffffu};
-    const uint32_t sv[4] = {sv4[k].x, sv4[k].y, sv4[k].z, sv4[k].w};
-    const uint32_t ev[4] = {ev4[k].x, ev4[k].y, ev4[k].z, ev4[k].w};
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-      uint32_t ok = uint32_t(e0 + uint32_t(k) * 256 + uint32_t(lane) * 4 + uint32_t(j) < n);
-      if (DUR) ok &= uint32_t(dv[j] >= lo) & uint32_t(dv[j] <= hi);
-      // req.Start <= endSeconds && req.End >= startSeconds (pipeline.go:62-63)
-      if (RANGE) ok &= uint32_t(start_s <= ev[j]) & uint32_t(end_s >= sv[j]);
-#pragma unroll
-      for (int q = 0; q < (NT > 0 ? NT : 1); q++) {
-        if (NT <= 0) break;
-        const uint32_t x = (tv[q][k] >> (8 * j)) & 0xffu;
-        const uint32_t wd = s_bm[((bmi4 >> (8 * q)) & 0xffu) * 8 + (x >> 5)];  // (x < 256: in the 256-bit map)
-        ok &= uint32_t(x < ((ns4 >> (8 * q)) & 0xffu)) & (wd >> (x & 31));
-      }
-      mask |= (ok & 1u) << (4 * k + j);
+  for (int k = kSteps - 1; k >= 0; k--) {
+    uint32_t w[4] = {0, 0, 0, 0};
+    if (DUR || RANGE) {
+      w[0] = R.d[k].x;
+      w[1] = R.d[k].y;
+      w[2] = R.d[k].z;
+      w[3] = R.d[k].w;
     }
+    bool esc_s = false, esc_e = false, slow = false;
+    if (RANGE) {
+      esc_s = ds_any_start_escaped(w[0], w[1], w[2], w[3]);
+      esc_e = ds_any_end_escaped(w[0], w[1], w[2], w[3]);
+      slow = esc_s | esc_e | !P.rng.fast;
+    }
+    uint32_t nib = 0;
+#pragma unroll
+    for (int j = 3; j >= 0; j--) {
+      bool ok = true;
+      if (DUR) ok = ds_dur_ok(w[j], P.dur);
+      if (RANGE) ok = ok & (slow | ds_range_ok(w[j], P.rng.e_lim, P.rng.s_lim));
+      if (NT > 0) {
+        uint32_t hits = 0;
+#pragma unroll
+        for (int q = 0; q < (NT > 0 ? NT : 1); q++) hits += s_tb[P.tb[q] + ((R.tv[q][k] >> (8 * j)) & 0xffu)];
+        ok = ok & (hits == uint32_t(NT));
+      }
+      nib = nib + nib + uint32_t(ok);
+    }
+    if (RANGE && slow) {
+      // req.Start <= endSeconds && req.End >= startSeconds (pipeline.go:62-63)
+      const uint64_t e = uint64_t(R.e0) + uint64_t(k) * 256 + uint64_t(lane) * 4;
+      u32x4 sv = {ds_start(w[0], P.sbase), ds_start(w[1], P.sbase), ds_start(w[2], P.sbase), ds_start(w[3], P.sbase)};
+      if (esc_s) sv = stream4<NTL>(scan + npad, e);
+      u32x4 ev = {ds_end(w[0], sv.x), ds_end(w[1], sv.y), ds_end(w[2], sv.z), ds_end(w[3], sv.w)};
+      if (esc_e) ev = stream4<NTL>(scan + 2ull * npad, e);
+      const uint32_t in = uint32_t((P.start_s <= ev.x) & (P.end_s >= sv.x)) |
+                          uint32_t((P.start_s <= ev.y) & (P.end_s >= sv.y)) << 1 |
+                          uint32_t((P.start_s <= ev.z) & (P.end_s >= sv.z)) << 2 |
+                          uint32_t((P.start_s <= ev.w) & (P.end_s >= sv.w)) << 3;
+      nib &= in;
+    }
+    mask = (mask << 4) | nib;
   }
+  const uint32_t nv = P.n - R.e0;  // (wave-uniform: only a block's last unit is cut)
+  if (nv < kPoolTile) mask &= ds_valid_mask(nv, uint32_t(lane));
   return mask;
 }
+
+// The launch's term tables: slot j of the bitmaps becomes s_tb[256 j ..], byte x = (x < ns) & bit x
+// (ds_word.hpp). One table dword per thread, so the build is a dozen instructions deep on every
+// wave, not a hundred on two (every wave waits for it at the staging barrier): dword i holds the
+// bytes 4 (i % 64) .. of slot i / 64, from bitmap word i / 8 (bmw) and the slot's set count
+// (PoolArgs::bm_ns); only the launch's nbms slots are built.
+constexpr uint32_t kTermDwords = uint32_t(kArgBms) * 64;
+__device__ __forceinline__ void stage_term_dword(uint8_t *s_tb, uint32_t i, uint32_t bmw, uint32_t ns) {
+  const uint32_t x0 = (i & 63u) * 4;
+  reinterpret_cast<uint32_t *>(s_tb)[i] = ds_term_word((bmw >> (x0 & 31u)) & 0xfu, x0, ns);
+}
+// (pool and static kernels: this thread's dword from the words it loaded ahead of the units'
+// loads; a workgroup of fewer than 1024 threads, TSG_POOL_WAVES, builds the rest from the kernel
+// arguments directly)
+template <int NT>
+__device__ __forceinline__ void stage_term_tables(uint8_t *s_tb, const PoolArgs &A, uint32_t xbm, uint32_t xns,
+                                                  uint32_t tid) {
+  if (NT <= 0) return;
+  const uint32_t n = min(A.nbms, uint32_t(kArgBms)) * 64;
+  if (tid < n) stage_term_dword(s_tb, tid, xbm, xns);
+  for (uint32_t i = tid + A.nthreads; i < n; i += A.nthreads)
+    stage_term_dword(s_tb, i, reinterpret_cast<const uint32_t *>(A.bms)[i >> 3], A.bm_ns[i >> 6]);
+}
+static_assert(kTermDwords <= kPoolThreads, "one table dword per thread of a full workgroup");
 
 // A workgroup barrier that waits for this wave's LDS and scalar-memory operations only
 // (lgkmcnt), not for its vector loads in flight: __syncthreads()' fence also waits
@@ -255,31 +337,6 @@ __device__ __forceinline__ uint32_t unit_mask(const u32x4 (&d)[kSteps], const u3
 // staging below reads the kernel arguments with scalar loads, so nothing it needs is
 // counted by vmcnt. (asm memory clobber: no LDS access moves across it)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-// Start and end seconds of a unit's entries, decoded from the ds column against the block's
-// base second (ds_word.hpp): start = base + rel, end = start + whole seconds of the duration +
-// carry. For a lane's four entries of a step where some start lies outside the 15-bit window
-// (rel 0x7fff) those four starts come from the exact start column, and where some duration
-// code is saturated (0xffff: durations from 32.768 s, ends before the start, e.g. the end = 0
-// entries of pitfall P1) those four ends from the exact end column (rare; only the lanes that
-// need them load: a unit-wide reload moved 16 MB more per config-2 query, the PMC count in
-// profiles/r04_final).
-template <bool NTL>
-__device__ __forceinline__ void unit_ends(const u32x4 (&ds)[kSteps], uint32_t sbase, u32x4 (&sv)[kSteps],
-                                          u32x4 (&ev)[kSteps], const uint32_t *scan, uint32_t npad, uint32_t e0,
-                                          int lane) {
-#pragma unroll
-  for (int k = 0; k < kSteps; k++) {
-    const uint32_t w[4] = {ds[k].x, ds[k].y, ds[k].z, ds[k].w};
-    const bool esc_s = ds_start_escaped(w[0]) || ds_start_escaped(w[1]) || ds_start_escaped(w[2]) || ds_start_escaped(w[3]);
-    const bool esc_e = ds_end_escaped(w[0]) || ds_end_escaped(w[1]) || ds_end_escaped(w[2]) || ds_end_escaped(w[3]);
-    const uint64_t e = uint64_t(e0) + uint64_t(k) * 256 + uint64_t(lane) * 4;
-    sv[k] = u32x4{ds_start(w[0], sbase), ds_start(w[1], sbase), ds_start(w[2], sbase), ds_start(w[3], sbase)};
-    if (esc_s) sv[k] = stream4<NTL>(scan + npad, e);
-    ev[k] = u32x4{ds_end(w[0], sv[k].x), ds_end(w[1], sv[k].y), ds_end(w[2], sv[k].z), ds_end(w[3], sv[k].w)};
-    if (esc_e) ev[k] = stream4<NTL>(scan + 2ull * npad, e);
-  }
-}
 
 // One match record (MatchRec: six words) into slot r of the LDS record buffer.
 __device__ __forceinline__ void put_rec(unsigned long long *s_rec, uint32_t r, const u32x4 &id, uint64_t st, uint64_t en,
@@ -368,7 +425,7 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_pool_kernel(PoolArgs A
   const unsigned long long t_start = A.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;
   __shared__ __attribute__((aligned(16))) PoolBlk s_blk[kArgSegs];
   __shared__ uint32_t s_ub[kArgSegs + 1], s_sb[kArgSegs];
-  __shared__ uint32_t s_bm[kArgBms * 8];
+  __shared__ __attribute__((aligned(16))) uint8_t s_tb[kArgBms * 256];  // the terms' byte tables
   __shared__ uint32_t s_chunk[kPoolChunks];
   __shared__ uint32_t s_next, s_nrec;
   extern __shared__ __attribute__((aligned(16))) unsigned long long s_rec[];  // rec_cap x 6 words
@@ -401,7 +458,8 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_pool_kernel(PoolArgs A
   const uint32_t xblk = uint32_t(tid) < nsegs * 16 ? blk_words[tid] : 0u;
   const uint32_t xub = uint32_t(tid) < nsegs ? A.blk[tid].ubase : units;
   const uint32_t xsb = uint32_t(tid) < nsegs ? A.sbase[tid] : 0u;
-  const uint32_t xbm = tid < kArgBms * 8 ? reinterpret_cast<const uint32_t *>(A.bms)[tid] : 0u;
+  const uint32_t xbm = NT > 0 ? reinterpret_cast<const uint32_t *>(A.bms)[tid >> 3] : 0u;  // (tid < 1024)
+  const uint32_t xns = NT > 0 ? A.bm_ns[tid >> 6] : 0u;
   const bool pre0 = wv < S, pre1 = wv + nwv < S;
   uint32_t ua = kPoolNone, ub = kPoolNone;
   if (pre0 && uint64_t(w) * S + wv < units) ua = w * S + wv;
@@ -411,11 +469,11 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_pool_kernel(PoolArgs A
   // ---- stage the launch's tables (scalar loads of the kernel arguments; the barrier does not
   // wait for the units' loads above)
   {
-    static_assert(kArgSegs * 16 <= kPoolThreads && kArgBms * 8 <= kPoolThreads, "one staging word per thread");
+    static_assert(kArgSegs * 16 <= kPoolThreads, "one staging word per thread");
     if (uint32_t(tid) < nsegs * 16) reinterpret_cast<uint32_t *>(s_blk)[tid] = xblk;
     if (uint32_t(tid) <= nsegs) s_ub[tid] = xub;
     if (uint32_t(tid) < nsegs) s_sb[tid] = xsb;
-    if (tid < kArgBms * 8) s_bm[tid] = xbm;
+    stage_term_tables<NT>(s_tb, A, xbm, xns, uint32_t(tid));
     for (uint32_t i = tid; i < kPoolChunks; i += A.nthreads) s_chunk[i] = kPoolPending;
     if (tid == 0) {
       s_next = min(2 * nwv, S);  // (the claims below it are the waves' first two)
@@ -494,11 +552,8 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_pool_kernel(PoolArgs A
   };
   auto eval = [&](const Unit &R) {
     const PoolBlk &B = s_blk[R.blk];
-    const uint32_t n = rfl(B.nent), bmi4 = rfl(B.bmi4), ns4 = rfl(B.nsets4);
-    u32x4 sv[kSteps], ev[kSteps];
-    if (RANGE) unit_ends<NTL>(R.d, rfl(s_sb[R.blk]), sv, ev, uniform_ptr(B.scan), rfl(B.npad), R.e0, lane);
-    uint32_t mask = unit_mask<NT, DUR, RANGE>(R.d, sv, ev, R.tv, R.e0, n, dlo, dhi, A.start_s, A.end_s, bmi4,
-                                               ns4, s_bm, lane);
+    const UnitPred<NT> P = unit_pred<NT>(dlo, dhi, A.start_s, A.end_s, rfl(s_sb[R.blk]), rfl(B.nent), rfl(B.bmi4));
+    uint32_t mask = unit_mask<NT, DUR, RANGE, NTL>(R, P, s_tb, uniform_ptr(B.scan), rfl(B.npad), lane);
     if (__ballot(mask != 0) == 0) return;
     if (A.unit_cap) mask = cap_unit_mask(mask, A.unit_cap, lane);
     put_unit(s_rec, &s_nrec, rec_cap, mask, A.desc[R.blk], rfl(B.block_idx), R.e0, lane);
@@ -543,7 +598,7 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_pool_kernel(PoolArgs A
 template <int NT, bool DUR, bool RANGE, bool NTL>
 __global__ void __launch_bounds__(kPoolThreads, 1) search_static_kernel(PoolArgs A) {
   const unsigned long long t_start = A.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;
-  __shared__ uint32_t s_bm[kArgBms * 8];
+  __shared__ __attribute__((aligned(16))) uint8_t s_tb[kArgBms * 256];  // the terms' byte tables
   __shared__ uint32_t s_nrec;
   extern __shared__ __attribute__((aligned(16))) unsigned long long s_rec[];  // rec_cap x 6 words
   const int tid = threadIdx.x, lane = tid & 63;
@@ -590,11 +645,8 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_static_kernel(PoolArgs
   // (evaluated right after the unit's load, while the block state still describes it)
   auto eval = [&](const Unit &R, uint32_t bslot) {
     const PoolBlk &P = A.blk[bslot];
-    const uint32_t n = P.nent, bmi4 = P.bmi4, ns4 = P.nsets4;
-    u32x4 sv[kSteps], ev[kSteps];
-    if (RANGE) unit_ends<NTL>(R.d, A.sbase[bslot], sv, ev, P.scan, P.npad, R.e0, lane);
-    uint32_t mask = unit_mask<NT, DUR, RANGE>(R.d, sv, ev, R.tv, R.e0, n, dlo, dhi, A.start_s, A.end_s, bmi4,
-                                               ns4, s_bm, lane);
+    const UnitPred<NT> U = unit_pred<NT>(dlo, dhi, A.start_s, A.end_s, A.sbase[bslot], P.nent, P.bmi4);
+    uint32_t mask = unit_mask<NT, DUR, RANGE, NTL>(R, U, s_tb, P.scan, P.npad, lane);
     if (__ballot(mask != 0) == 0) return;
     if (A.unit_cap) mask = cap_unit_mask(mask, A.unit_cap, lane);
     put_unit(s_rec, &s_nrec, rec_cap, mask, A.desc[bslot], P.block_idx, R.e0, lane);
@@ -603,12 +655,13 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_static_kernel(PoolArgs
   // completion: their wait does not wait for those); the first unit's loads are
   // unconditional (a wave without units reloads the launch's last unit), so every path issues
   // the same loads after these
-  const uint32_t xbm = tid < kArgBms * 8 ? reinterpret_cast<const uint32_t *>(A.bms)[tid] : 0u;
+  const uint32_t xbm = NT > 0 ? reinterpret_cast<const uint32_t *>(A.bms)[tid >> 3] : 0u;  // (tid < 1024)
+  const uint32_t xns = NT > 0 ? A.bm_ns[tid >> 6] : 0u;
   Unit ra, rb;
   uint32_t u = u_begin, ba = b, bb = b;
   load(ra, u < u_end ? u : (units ? units - 1 : 0u));
   ba = b;
-  if (tid < kArgBms * 8) s_bm[tid] = xbm;
+  stage_term_tables<NT>(s_tb, A, xbm, xns, uint32_t(tid));
   if (tid == 0) s_nrec = 0;
   lds_barrier();  // (not waiting for the first unit's loads)
   stamp_begin(A.stamps, w, t_start, tid);
@@ -710,6 +763,7 @@ constexpr uint32_t kResMaxRecs = uint32_t(kPoolLds / sizeof(MatchRec));  // the 
 template <int NT, bool DUR, bool RANGE, bool NTL>
 __global__ void __launch_bounds__(kResThreads, 1) search_resident_kernel(ResidentArgs R) {
   __shared__ __attribute__((aligned(16))) uint32_t s_args[sizeof(PoolArgs) / 4];
+  __shared__ __attribute__((aligned(16))) uint8_t s_tb[kArgBms * 256];  // the terms' byte tables
   __shared__ uint32_t s_ctl[4];   // [0] command for this round, [1] checksum, [2] header seq, [3] header csum
   __shared__ uint32_t s_wn[kPoolWaves + 1];
   __shared__ uint32_t s_ub[kResMaxUnits], s_uc[kResMaxUnits];  // per unit of the run: LDS record base, count
@@ -855,13 +909,6 @@ __global__ void __launch_bounds__(kResThreads, 1) search_resident_kernel(Residen
     const uint32_t rec_cap = rfl(A.rec_cap);
     const uint32_t dlo = rfl(A.has_min ? A.min32 : 0u), dhi = rfl(A.has_max ? A.max32 : 0xffffffffu);
     const uint32_t start_s = rfl(A.start_s), end_s = rfl(A.end_s), ucap = rfl(A.unit_cap);
-    const uint32_t *s_bm = reinterpret_cast<const uint32_t *>(A.bms);
-    for (uint32_t i = uint32_t(tid); i < nk; i += nthreads) s_uc[i] = 0;
-    if (tid == 0) {
-      s_next = 0;
-      s_nrec = 0;
-    }
-    __syncthreads();
     // the block of the wave's last load (its fields are read from LDS per load); from the
     // block holding the run's first unit (a walk from block 0 had put up to nsegs dependent LDS
     // reads before a late workgroup's first loads)
@@ -899,11 +946,8 @@ __global__ void __launch_bounds__(kResThreads, 1) search_resident_kernel(Residen
       Pd.has = false;
       const uint32_t blk = block_of(A.ubase, nsegs, ua + Rg.k, lane);
       const PoolBlk &P = A.blk[blk];
-      const uint32_t n = rfl(P.nent), bmi4 = rfl(P.bmi4), ns4 = rfl(P.nsets4);
-      u32x4 sv[kSteps], ev[kSteps];
-      if (RANGE) unit_ends<NTL>(Rg.d, rfl(A.sbase[blk]), sv, ev, uniform_ptr(P.scan), rfl(P.npad), Rg.e0, lane);
-      uint32_t mask = unit_mask<NT, DUR, RANGE>(Rg.d, sv, ev, Rg.tv, Rg.e0, n, dlo, dhi, start_s, end_s, bmi4, ns4,
-                                                 s_bm, lane);
+      const UnitPred<NT> U = unit_pred<NT>(dlo, dhi, start_s, end_s, rfl(A.sbase[blk]), rfl(P.nent), rfl(P.bmi4));
+      uint32_t mask = unit_mask<NT, DUR, RANGE, NTL>(Rg, U, s_tb, uniform_ptr(P.scan), rfl(P.npad), lane);
       if (__ballot(mask != 0) == 0) return;
       if (ucap) mask = cap_unit_mask(mask, ucap, lane);
       uint32_t cnt = uint32_t(__popc(mask));
@@ -975,6 +1019,18 @@ __global__ void __launch_bounds__(kResThreads, 1) search_resident_kernel(Residen
     uint32_t ka = wave, kb = wave + nwv;
     if (ka < nk) load(ra, ka);
     if (kb < nk) load(rb, kb);
+    // the query's LDS tables once the first loads are out (they read the arguments only): the
+    // units' counts, the claim and record counters, the terms' byte tables; the barrier waits for
+    // LDS alone, not for those loads
+    for (uint32_t i = uint32_t(tid); i < nk; i += nthreads) s_uc[i] = 0;
+    if (NT > 0)
+      for (uint32_t i = uint32_t(tid), n = min(rfl(A.nbms), uint32_t(kArgBms)) * 64; i < n; i += nthreads)
+        stage_term_dword(s_tb, i, reinterpret_cast<const uint32_t *>(A.bms)[i >> 3], A.bm_ns[i >> 6]);
+    if (tid == 0) {
+      s_next = 0;
+      s_nrec = 0;
+    }
+    lds_barrier();
     // a unit's gathers are stored one unit later (eval_b of unit n of a stream runs before
     // eval_a of unit n+1 of the same stream): by then the loads issued after them are being
     // waited for anyway (vector loads complete in order), so a match costs the wave no stall
