@@ -230,8 +230,10 @@ __device__ __forceinline__ uint32_t cap_unit_mask(uint32_t mask, uint32_t cap, i
 // where a start escaped, ends from the exact end column where an end did (rare; only the lanes
 // that need them load: a unit-wide reload moved 16 MB more per config-2 query, the PMC count in
 // profiles/r04_final). That decode sits under a per-lane branch, as the reloads always did: only
-// the lanes that need it run it, the others wait for them (not a wave-uniform branch; with 0.1 %
-// of the entries escaped about a fifth of a wave's steps take it).
+// the lanes that need it run it, the others wait for them (not a wave-uniform branch). A lane
+// needs it when one of its four entries has passed everything else: with 0.1 % of the entries
+// escaped about a fifth of a wave's steps hold an escaped word, but few of those an entry the
+// terms and the duration let through, and the reloads drain the wave's loads in flight.
 template <int NT>
 struct UnitPred {
   DsDur dur;
@@ -286,7 +288,9 @@ __device__ __forceinline__ uint32_t unit_mask(const UnitRegs<NT> &R, const UnitP
       }
       nib = nib + nib + uint32_t(ok);
     }
-    if (RANGE && slow) {
+    // (only a lane that can still match: the terms, the duration and, where the word's tests hold,
+    // the range are in nib already, and nib &= in leaves a zero nib as it is)
+    if (RANGE && slow && nib != 0) {
       // req.Start <= endSeconds && req.End >= startSeconds (pipeline.go:62-63)
       const uint64_t e = uint64_t(R.e0) + uint64_t(k) * 256 + uint64_t(lane) * 4;
       u32x4 sv = {ds_start(w[0], P.sbase), ds_start(w[1], P.sbase), ds_start(w[2], P.sbase), ds_start(w[3], P.sbase)};
@@ -1036,6 +1040,37 @@ __global__ void __launch_bounds__(kResThreads, 1) search_resident_kernel(Residen
     // waited for anyway (vector loads complete in order), so a match costs the wave no stall
     Pend pa, pb;
     pa.has = pb.has = false;
+    // ---- the steady state: both streams hold a unit and every claim yields one, so a stream's
+    // next loads are issued with no branch around them. The compiler's count of the loads in
+    // flight is then exact where it matters: the wait before a unit's registers are first used
+    // leaves the other stream's eight loads outstanding (vmcnt >= 8). With the loads under
+    // `if (k < nk)` the count at that wait was merged with the path that skips them, to 0: every
+    // unit drained the loads just issued, one unit in flight per wave, not two
+    // (profiles/res_inflight). Stream a's first unit is evaluated ahead of the loop: at a loop
+    // head its wait would be merged with the entry path, where the first two loads are
+    // conditional. The units, the claims and their order are those of the loop below, which
+    // takes over as soon as a claim comes back past the run (and is all a wave with two units or
+    // fewer runs).
+    if (ka < nk && kb < nk) {
+      eval_b(pa);
+      eval_a(ra, pa);
+      ka = claim(ka);
+      if (ka < nk) {
+        load(ra, ka);
+        for (;;) {
+          eval_b(pb);
+          eval_a(rb, pb);
+          kb = claim(kb);
+          if (kb >= nk) break;
+          load(rb, kb);
+          eval_b(pa);
+          eval_a(ra, pa);
+          ka = claim(ka);
+          if (ka >= nk) break;
+          load(ra, ka);
+        }
+      }
+    }
     while (ka < nk || kb < nk) {
       if (ka < nk) {
         eval_b(pa);

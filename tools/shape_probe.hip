@@ -1,20 +1,31 @@
 // shape_probe.hip — measurement tool (not part of libtsg): how fast can one launch stream the
-// main line's filter columns (10 M entries: ds u32, start_s u32, three 1-byte tag columns =
-// 11 B/entry, 110 MB) with the resident kernel's access shape, and which part of that shape
-// costs what. Four disjoint copies are swept in turn (440 MB > the 256 MiB Infinity Cache), as
+// main line's filter columns (10 M entries: the packed scan word u32 and three 1-byte tag columns
+// = 7 B/entry, 70 MB) with the resident kernel's access shape, and which part of that shape
+// costs what. Four disjoint copies are swept in turn (280 MB > the 256 MiB Infinity Cache), as
 // the bench's main line does. Each mode is timed with hipEvents over `reps` launches.
 //
-//   mode 0  the search kernels' shape: 512-entry units, per lane 2 x (ds, start) 16-B loads and
-//           2 x 3 tag 4-B loads (lane l: entries k*256 + 4l .. +3)
+//   mode 0  the search kernels' shape: 512-entry units, per lane 2 x 16-B loads of the scan word
+//           and 2 x 3 tag 4-B loads (lane l: entries k*256 + 4l .. +3): 3,584 B per unit
 //   mode 1  the same with the tag columns read by 16-B loads (lanes 0..31, 512 B per column)
-//   mode 2  the ds and start columns alone (16-B loads; 8 B/entry)
-//   mode 3  the same 5,632 B per unit as one contiguous array, 16-B loads (the shape's ceiling)
+//   mode 2  the scan word alone (16-B loads; 4 B/entry)
+//   mode 3  the same 3,584 B per unit as one contiguous array, 16-B loads (the shape's ceiling)
 //
 // Workgroups: 256 x (waves x 64); each owns a contiguous unit run (equal shares), its waves
 // take the run's units from an LDS counter, two units in flight per wave (the search kernels'
-// pipelining). Build: hipcc -O3 --offload-arch=gfx950 tools/shape_probe.hip -o tools/_bin/shape_probe
+// pipelining). The unit loop comes in three forms:
+//
+//   (plain)  a stream's next loads under `if (k < nk)`: the compiler's count of the loads in
+//            flight is merged with the path that skips them, and the wait for a unit drains the
+//            other stream's loads too (one unit in flight)
+//   x        every trip issues both streams' loads (a unit past the run re-reads the run's last
+//            unit, L2-hot): the counts are exact, two units in flight
+//   p        the resident kernel's loop: the steady state peeled, its loads unconditional, the
+//            plain loop for the last units; no load is issued twice
+//
+// Build: hipcc -O3 --offload-arch=gfx950 tools/shape_probe.hip -o tools/_bin/shape_probe
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -30,11 +41,12 @@
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 constexpr uint32_t kUnit = 512;
+constexpr uint32_t kUnitBytes = kUnit * 7;  // 3584 = 3.5 x 1024
 
 struct Set {
-  const uint32_t *ds, *st;
+  const uint32_t *ds;
   const uint8_t *t[3];
-  const uint8_t *flat;  // mode 3: 5632 B per unit
+  const uint8_t *flat;  // mode 3: 3584 B per unit
 };
 
 template <bool NT>
@@ -49,30 +61,26 @@ __device__ __forceinline__ uint32_t ld1(const void *p) {
 }
 
 struct Regs {
-  u32x4 a[2], b[2];
+  u32x4 a[2];
   u32x4 t4[3];
   uint32_t t[3][2];
-  u32x4 f[6];
+  u32x4 f[4];
 };
 
 template <int MODE, bool NT>
 __device__ __forceinline__ void load(Regs &R, const Set &S, uint32_t u, int lane) {
   const uint64_t e0 = uint64_t(u) * kUnit;
   if (MODE == 3) {
-    const uint8_t *p = S.flat + uint64_t(u) * (kUnit * 11);
+    const uint8_t *p = S.flat + uint64_t(u) * kUnitBytes;
 #pragma unroll
-    for (int k = 0; k < 6; k++) {  // 5632 B = 5.5 x 1024: the last load by lanes 0..31
+    for (int k = 0; k < 4; k++) {  // the last load by lanes 0..31
       const uint32_t off = k * 1024 + lane * 16;
-      R.f[k] = off < kUnit * 11 ? ld4<NT>(p + off) : u32x4{0, 0, 0, 0};
+      R.f[k] = off < kUnitBytes ? ld4<NT>(p + off) : u32x4{0, 0, 0, 0};
     }
     return;
   }
 #pragma unroll
-  for (int k = 0; k < 2; k++) {
-    const uint64_t e = e0 + k * 256 + lane * 4;
-    R.a[k] = ld4<NT>(S.ds + e);
-    R.b[k] = ld4<NT>(S.st + e);
-  }
+  for (int k = 0; k < 2; k++) R.a[k] = ld4<NT>(S.ds + e0 + k * 256 + lane * 4);
   if (MODE == 0) {
 #pragma unroll
     for (int q = 0; q < 3; q++)
@@ -89,11 +97,11 @@ __device__ __forceinline__ uint32_t use(const Regs &R) {
   uint32_t x = 0;
   if (MODE == 3) {
 #pragma unroll
-    for (int k = 0; k < 6; k++) x ^= R.f[k].x ^ R.f[k].y ^ R.f[k].z ^ R.f[k].w;
+    for (int k = 0; k < 4; k++) x ^= R.f[k].x ^ R.f[k].y ^ R.f[k].z ^ R.f[k].w;
     return x;
   }
 #pragma unroll
-  for (int k = 0; k < 2; k++) x ^= R.a[k].x ^ R.a[k].y ^ R.a[k].z ^ R.a[k].w ^ R.b[k].x ^ R.b[k].y ^ R.b[k].z ^ R.b[k].w;
+  for (int k = 0; k < 2; k++) x ^= R.a[k].x ^ R.a[k].y ^ R.a[k].z ^ R.a[k].w;
   if (MODE == 0)
 #pragma unroll
     for (int q = 0; q < 3; q++) x ^= R.t[q][0] ^ R.t[q][1];
@@ -103,7 +111,9 @@ __device__ __forceinline__ uint32_t use(const Regs &R) {
   return x;
 }
 
-template <int MODE, bool NT, bool EXACT = false>
+enum Loop { kPlain = 0, kExact = 1, kPeeled = 2 };
+
+template <int MODE, bool NT, int LOOP = kPlain>
 __global__ void __launch_bounds__(1024, 1) probe(Set S, uint32_t nunits, uint32_t *out) {
   __shared__ uint32_t s_next;
   const int lane = threadIdx.x & 63;
@@ -119,10 +129,7 @@ __global__ void __launch_bounds__(1024, 1) probe(Set S, uint32_t nunits, uint32_
   };
   Regs ra, rb;
   uint32_t ka = wave, kb = wave + nwv, acc = 0;
-  if constexpr (EXACT) {
-    // every iteration issues both streams' loads (a unit past the run re-reads the run's first
-    // unit, L2-hot): the compiler's vmcnt bookkeeping stays exact, so the wait for one unit's
-    // data does not also wait for the other unit's loads (two units in flight, not one)
+  if constexpr (LOOP == kExact) {
     load<MODE, NT>(ra, S, ua + min(ka, nk - 1), lane);
     load<MODE, NT>(rb, S, ua + min(kb, nk - 1), lane);
     while (ka < nk || kb < nk) {
@@ -140,6 +147,25 @@ __global__ void __launch_bounds__(1024, 1) probe(Set S, uint32_t nunits, uint32_
   }
   if (ka < nk) load<MODE, NT>(ra, S, ua + ka, lane);
   if (kb < nk) load<MODE, NT>(rb, S, ua + kb, lane);
+  if constexpr (LOOP == kPeeled) {
+    if (ka < nk && kb < nk) {
+      acc ^= use<MODE>(ra);
+      ka = claim();
+      if (ka < nk) {
+        load<MODE, NT>(ra, S, ua + ka, lane);
+        for (;;) {
+          acc ^= use<MODE>(rb);
+          kb = claim();
+          if (kb >= nk) break;
+          load<MODE, NT>(rb, S, ua + kb, lane);
+          acc ^= use<MODE>(ra);
+          ka = claim();
+          if (ka >= nk) break;
+          load<MODE, NT>(ra, S, ua + ka, lane);
+        }
+      }
+    }
+  }
   while (ka < nk || kb < nk) {
     if (ka < nk) {
       acc ^= use<MODE>(ra);
@@ -155,17 +181,17 @@ __global__ void __launch_bounds__(1024, 1) probe(Set S, uint32_t nunits, uint32_
   if (acc == 0x9E3779B9u) out[w] = acc;  // (keeps the loads; never true in practice)
 }
 
-template <int MODE, bool NT, bool EXACT = false>
+template <int MODE, bool NT, int LOOP = kPlain>
 static void run(const std::vector<Set> &sets, uint32_t nunits, int waves, int reps, uint32_t *out, double bytes) {
   hipEvent_t a, b;
   CK(hipEventCreate(&a));
   CK(hipEventCreate(&b));
-  for (int i = 0; i < 8; i++) probe<MODE, NT, EXACT><<<256, waves * 64>>>(sets[i % sets.size()], nunits, out);
+  for (int i = 0; i < 8; i++) probe<MODE, NT, LOOP><<<256, waves * 64>>>(sets[i % sets.size()], nunits, out);
   CK(hipDeviceSynchronize());
   std::vector<float> ms;
   for (int i = 0; i < reps; i++) {
     CK(hipEventRecord(a));
-    probe<MODE, NT, EXACT><<<256, waves * 64>>>(sets[i % sets.size()], nunits, out);
+    probe<MODE, NT, LOOP><<<256, waves * 64>>>(sets[i % sets.size()], nunits, out);
     CK(hipEventRecord(b));
     CK(hipEventSynchronize(b));
     float t = 0;
@@ -174,8 +200,21 @@ static void run(const std::vector<Set> &sets, uint32_t nunits, int waves, int re
   }
   std::sort(ms.begin(), ms.end());
   const double med = ms[ms.size() / 2] * 1e3, best = ms[0] * 1e3;
-  std::printf("mode %d%s nt %d waves %2d: median %7.2f us  best %7.2f us  -> %6.0f GB/s (11 B/entry basis %6.0f)\n", MODE,
-              EXACT ? "x" : " ", int(NT), waves, med, best, bytes / med / 1e3, 110.0e6 / med / 1e3);
+  std::printf("mode %d%c nt %d waves %2d: median %7.2f us  best %7.2f us  -> %6.0f GB/s (7 B/entry basis %6.0f)\n", MODE,
+              " xp"[LOOP], int(NT), waves, med, best, bytes / med / 1e3, 70.0e6 / med / 1e3);
+  CK(hipEventDestroy(a));
+  CK(hipEventDestroy(b));
+}
+
+static void sweep(const std::vector<Set> &sets, uint32_t nunits, int waves, int reps, uint32_t *out, double b7, double b4) {
+  run<0, true>(sets, nunits, waves, reps, out, b7);
+  run<0, true, kExact>(sets, nunits, waves, reps, out, b7);
+  run<0, true, kPeeled>(sets, nunits, waves, reps, out, b7);
+  run<0, false>(sets, nunits, waves, reps, out, b7);
+  run<1, true>(sets, nunits, waves, reps, out, b7);
+  run<2, true>(sets, nunits, waves, reps, out, b4);
+  run<3, true>(sets, nunits, waves, reps, out, b7);
+  run<3, true, kExact>(sets, nunits, waves, reps, out, b7);
 }
 
 int main(int argc, char **argv) {
@@ -185,25 +224,16 @@ int main(int argc, char **argv) {
   std::vector<Set> sets(nsets);
   for (int s = 0; s < nsets; s++) {
     uint8_t *p = nullptr;
-    const size_t bytes = N * 11;
+    const size_t bytes = N * 7;
     CK(hipMalloc(&p, bytes * 2));  // columns, then the flat copy
     CK(hipMemset(p, s + 1, bytes * 2));
     sets[s].ds = reinterpret_cast<const uint32_t *>(p);
-    sets[s].st = reinterpret_cast<const uint32_t *>(p + N * 4);
-    for (int q = 0; q < 3; q++) sets[s].t[q] = p + N * 8 + N * q;
+    for (int q = 0; q < 3; q++) sets[s].t[q] = p + N * 4 + N * q;
     sets[s].flat = p + bytes;
   }
   uint32_t *out = nullptr;
   CK(hipMalloc(&out, 256 * 4));
-  const double b11 = double(N) * 11, b8 = double(N) * 8;
-  for (int waves : {8, 12, 16}) {
-    run<0, true, true>(sets, nunits, waves, reps, out, b11);
-    run<3, true, true>(sets, nunits, waves, reps, out, b11);
-    run<0, true>(sets, nunits, waves, reps, out, b11);
-    run<0, false>(sets, nunits, waves, reps, out, b11);
-    run<1, true>(sets, nunits, waves, reps, out, b11);
-    run<2, true>(sets, nunits, waves, reps, out, b8);
-    run<3, true>(sets, nunits, waves, reps, out, b11);
-  }
+  const double b7 = double(N) * 7, b4 = double(N) * 4;
+  for (int waves : {8, 12, 16}) sweep(sets, nunits, waves, reps, out, b7, b4);
   return 0;
 }
