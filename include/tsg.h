@@ -211,6 +211,7 @@ int tsg_device_numa_node(tsg_ctx *ctx, int dev);
  * a read that caught the host's writes landing), [5] narrow queries launched plainly because
  * another process has a libtsg context on the same GPU, [6] narrow queries launched plainly
  * (any reason), [7] samples taken for the XCD-weighted split. Zeros when TSG_RESIDENT=0.
+ * [8] narrow queries served by a terms-first kernel instance (resident or plain launches).
  * DESIGN.md §4. */
 int tsg_device_counters(tsg_ctx *ctx, int dev, uint64_t *out, size_t n);
 const char *tsg_last_error(void);
@@ -390,7 +391,9 @@ int tsg_search_batch(tsg_ctx *ctx, const tsg_search_item *items, size_t n, uint3
  * words moved by +-d: the plain sum unchanged) and repair it 200 us later; the kernel must
  * re-read the slot (tsg_device_counters[4] counts the rejected reads). "groups" = n (0 = the
  * device's CUs): search launches plan for n CUs. "xsplit" = 0/1: the resident kernel's
- * XCD-weighted split (default TSG_RES_XSPLIT, off). "lb_bitmap" = 0/1/2: full scans on the
+ * XCD-weighted split (default TSG_RES_XSPLIT, off). "terms_first" = 0/1/2: the narrow kernels
+ * read the packed scan word only where the terms pass never / wherever the instance exists / when
+ * the blocks' counted selectivities say so (default TSG_TERMS_FIRST, 2). "lb_bitmap" = 0/1/2: full scans on the
  * dictionary-pass path return one bit per entry never / always / after a dense one (default
  * TSG_LB_BITMAP, 2). "proto_batch_jobs" = k: tsg_proto_search_batch launches cover at most k jobs
  * (0 = the default, 4096). "dict_stream_min" = b: a key's dictionary of more than b bytes is

@@ -3,6 +3,7 @@
 // flatbuffer is walked once per distinct KeyValues table (tables are shared
 // between entries of a page by writeKeyValues' cache, searchdatamap.go:115-128).
 #include "block.hpp"
+#include "terms_first.hpp"
 
 #include <algorithm>
 #include <cctype>
@@ -1280,6 +1281,7 @@ void decode_search_block(const uint8_t *meta, size_t meta_len, bool meta_present
   load_pages(hb, recs, data, data_len, nthreads);
   const auto tc0 = clk::now();
   canonicalize_narrow_keys(hb);
+  count_narrow_sets(hb);
   const auto tc1 = clk::now();
   verify_header_dicts(hb, nthreads);
   // byte-pair counts of the large dictionaries: 64 windows of 16 KiB spread over the bytes
@@ -1571,6 +1573,15 @@ void splice_entries(const WalRefreshPlan &p, const V &o, const V &dl, size_t w, 
 }
 }  // namespace
 
+void count_narrow_sets(HostBlock &hb) {
+  for (auto &kc : hb.keys) {
+    kc.set_count.clear();
+    if (kc.width() != 1 || kc.col.size() != hb.n) continue;
+    kc.set_count.resize(kc.nsets());
+    count_sets(kc.col.data(), kc.col.size(), kc.nsets(), kc.set_count.data());
+  }
+}
+
 void trim_uploaded_host(HostBlock &hb) {
   for (size_t k = 0; k < hb.keys.size(); k++) {
     auto &kc = hb.keys[k];
@@ -1619,6 +1630,7 @@ void decode_wal_search_block(const uint8_t *file, size_t len, int enc, HostBlock
   for (auto &kc : hb.keys) kc.col.resize(hb.n, kNone);
   for (const auto &kc : hb.keys) ws->keys.push_back(dict_only(kc));
   canonicalize_narrow_keys(hb, &ws->vcanon, &ws->scanon);
+  count_narrow_sets(hb);
   hb.wal = std::move(ws);
 }
 
@@ -1850,6 +1862,7 @@ void decode_live_block(const uint8_t *bytes, const uint64_t *seg_off, uint64_t n
         for (uint32_t j = kc.set_off[s]; j < kc.set_off[s + 1]; j++) dst.insert(std::string(hb.dict_value(int(k), kc.set_vals[j])));
   }
   canonicalize_narrow_keys(hb);
+  count_narrow_sets(hb);
 }
 
 }  // namespace tsg

@@ -120,6 +120,12 @@ struct KeyColumn {
   std::vector<uint32_t> set_vals;  // value ids, in vector order (descending bytes)
   bool identity = true;            // every set is {v} with set id == value id
   std::vector<uint32_t> col;       // per entry: set id or kNone (key absent)
+  // one-byte keys: the entries per value-set id (nsets counters, counted from `col` where a loader
+  // has numbered it for good: count_narrow_sets), kept after `col` is trimmed and shared by clones
+  // with the rest of the host side. The narrow scan's planner estimates a term's selectivity from
+  // them (terms_first.hpp). Empty: never counted (a refreshed WAL block, whose merged column exists
+  // only on the device), and the planner then keeps the kernels' default mode.
+  std::vector<uint32_t> set_count;
   // large dictionaries (> kDeferMinBytes): counts of each adjacent byte pair (b0 << 8 | b1) in
   // a sample of the value bytes; the dictionary stream pass tests a needle's rarest pair
   std::vector<uint32_t> pair_freq;
@@ -284,6 +290,9 @@ void plan_wal_refresh(const HostBlock &old, const uint8_t *file, uint64_t base, 
                       WalRefreshPlan &plan);
 // What stays on the host once the device holds a block's columns (capi.cpp open_common).
 void trim_uploaded_host(HostBlock &hb);
+// KeyColumn::set_count of every one-byte key, from its column (the loaders call it once the
+// narrow keys have their canonical numbering: the ids counted are the bytes the device scans).
+void count_narrow_sets(HostBlock &hb);
 
 // Live traces: segment i = bytes[seg_off[i], seg_off[i+1]) (a SearchEntry flatbuffer as the
 // distributor wrote it), trace t = segments [trace_seg[t], trace_seg[t+1]). Every segment is

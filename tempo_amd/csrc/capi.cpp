@@ -764,9 +764,9 @@ int tsg_device_numa_node(tsg_ctx *ctx, int dev) {
 int tsg_device_counters(tsg_ctx *ctx, int dev, uint64_t *out, size_t n) {
   if (!ctx || !out || dev < 0 || size_t(dev) >= ctx->c.devs.size()) return TSG_E_INVALID;
   return guard([&] {
-    uint64_t c[8];
+    uint64_t c[9];
     device_counters(*ctx->c.devs[size_t(dev)], c);
-    for (size_t i = 0; i < n; i++) out[i] = i < 8 ? c[i] : 0;
+    for (size_t i = 0; i < n; i++) out[i] = i < 9 ? c[i] : 0;
   });
 }
 int tsg_cancel(tsg_ctx *ctx, uint64_t qid) {

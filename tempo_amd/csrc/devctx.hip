@@ -61,7 +61,7 @@ void pinned_put(void *p, size_t) {
     g_pin_free.erase(it);
   }
 }
-void device_counters(DeviceCtx &dc, uint64_t out[8]) {
+void device_counters(DeviceCtx &dc, uint64_t out[9]) {
   std::lock_guard<std::mutex> lk(dc.mu);
   out[0] = dc.res_launches;
   out[1] = dc.res_queries;
@@ -71,6 +71,7 @@ void device_counters(DeviceCtx &dc, uint64_t out[8]) {
   out[5] = dc.res_cotenant_queries;
   out[6] = dc.res_plain_queries;
   out[7] = dc.res_xsamples;
+  out[8] = dc.tf_queries;
 }
 
 void ctx_init(Ctx &c, const tsg_options *opts) {

@@ -184,6 +184,8 @@ struct DeviceCtx {
   bool res_on = env_u32("TSG_RESIDENT", 1, 0, 1) != 0;
   // (TSG_RESIDENT_IDLE_US, read at each launch: the idle timeout in us, default 10000)
   uint64_t res_launches = 0, res_queries = 0, res_relaunches = 0, res_quits = 0;  // tsg_device_counters
+  uint64_t tf_queries = 0;  // narrow launches / resident queries served by a terms-first instance
+  uint32_t tf_streak = 0;  // auto mode: queries in a row that asked for terms first while the live launch is the default instance
   uint8_t *res_mem = nullptr;
   uint32_t res_seq = 0;  // last posted sequence number
   bool res_alive = false;

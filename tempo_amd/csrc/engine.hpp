@@ -249,8 +249,9 @@ void device_find(DeviceCtx &dc, const std::vector<std::pair<uint32_t, V2Block *>
                  size_t nids, const tsg_lookup_opts *opts, FindOut &out);
 
 int device_ordinal(const DeviceCtx &dc);
-// resident search counters: launches, queries served, relaunches after an idle-exit race, quits
-void device_counters(DeviceCtx &dc, uint64_t out[8]);
+// resident search counters: launches, queries served, relaunches after an idle-exit race, quits,
+// ...; [8] = the narrow queries a terms-first instance served (resident, pool or static kernel)
+void device_counters(DeviceCtx &dc, uint64_t out[9]);
 // The last full scan on the device's dictionary-pass path had more than one match per 64
 // entries (search.hip: its next full scans there return bitmaps; tsg_search pipelines them)
 bool device_last_dense(DeviceCtx &dc);
@@ -263,7 +264,8 @@ uint64_t resident_batch_begin(DeviceCtx &dc);
 uint64_t resident_batch_end(DeviceCtx &dc, uint64_t launches_before);
 // test hooks (tsg_debug_set): "res_torn", "groups" (search launches plan for this many CUs:
 // e.g. 8 makes a resident query of 6 M entries run > 1536 units per workgroup), "xsplit"
-// (0/1: the resident kernel's XCD-weighted split; default TSG_RES_XSPLIT, 0)
+// (0/1: the resident kernel's XCD-weighted split; default TSG_RES_XSPLIT, 0), "terms_first" (the
+// narrow kernels' mode: 0 off / 1 forced / 2 auto; default TSG_TERMS_FIRST, 2)
 int debug_set(const char *name, int64_t value);
 void find_zstd_lane(bool on);  // find.hip ("zstd_find_lane": 1 = the one-lane zstd page decoder)
 void proto_batch_cap(uint32_t k);  // proto_scan.hip ("proto_batch_jobs": jobs per batched launch, 0 = the default)

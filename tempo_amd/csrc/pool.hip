@@ -28,20 +28,31 @@
 #include "aql.hpp"
 #include "pool_kernels.hpp"
 #include "search_common.hpp"
+#include "terms_first.hpp"
 
 namespace tsg {
 
 // ------------------------------------------------------------------------------------
 // host: the kernels' instances
 //
-// A query's shape (terms clamped to 4, duration filter, time range, non-temporal loads) as
-// compile-time constants: f(nt, dur, range, ntl) is called with std::integral_constants.
+// A query's shape (terms clamped to 4, duration filter, time range, non-temporal loads, terms
+// first) as compile-time constants: f(nt, dur, range, ntl, tf) is called with
+// std::integral_constants. Terms first exists only for shapes with a term and a filter on the scan
+// word (kTermsFirstShape): any other shape resolves to the instance it always had.
+static bool terms_first_shape(uint32_t nterms, bool dur, bool range) { return nterms > 0 && (dur || range); }
 template <class F>
-static auto with_shape(uint32_t nterms, bool dur, bool range, bool ntl, F &&f) {
+static auto with_shape(uint32_t nterms, bool dur, bool range, bool ntl, bool tf, F &&f) {
   auto flag = [](bool v, auto &&g) { return v ? g(std::true_type{}) : g(std::false_type{}); };
   auto flags = [&](auto nt) {
     return flag(dur, [&](auto d) {
-      return flag(range, [&](auto r) { return flag(ntl, [&](auto n) { return f(nt, d, r, n); }); });
+      return flag(range, [&](auto r) {
+        return flag(ntl, [&](auto n) {
+          if constexpr (kTermsFirstShape<nt(), d(), r()>) {
+            if (tf) return f(nt, d, r, n, std::true_type{});
+          }
+          return f(nt, d, r, n, std::false_type{});
+        });
+      });
     });
   };
   switch (nterms) {
@@ -54,25 +65,26 @@ static auto with_shape(uint32_t nterms, bool dur, bool range, bool ntl, F &&f) {
 }
 enum class Kernel { pool, stat, resident };
 using PoolFn = void (*)(PoolArgs);
-static PoolFn pool_fn(Kernel kind, uint32_t nterms, bool dur, bool range, bool ntl) {
-  return with_shape(nterms, dur, range, ntl, [&](auto nt, auto d, auto r, auto n) -> PoolFn {
-    if (kind == Kernel::stat) return search_static_kernel<nt(), d(), r(), n()>;
-    return search_pool_kernel<nt(), d(), r(), n()>;
+static PoolFn pool_fn(Kernel kind, uint32_t nterms, bool dur, bool range, bool ntl, bool tf) {
+  return with_shape(nterms, dur, range, ntl, tf, [&](auto nt, auto d, auto r, auto n, auto t) -> PoolFn {
+    if (kind == Kernel::stat) return search_static_kernel<nt(), d(), r(), n(), t()>;
+    return search_pool_kernel<nt(), d(), r(), n(), t()>;
   });
 }
 // (every resident instantiation referenced, so that the code object beside libtsg.so holds them
 // all: the resident kernel is launched by symbol through the AQL queue only)
-[[maybe_unused]] static void *resident_fn(uint32_t nterms, bool dur, bool range, bool ntl) {
-  return with_shape(nterms, dur, range, ntl, [](auto nt, auto d, auto r, auto n) {
-    return reinterpret_cast<void *>(search_resident_kernel<nt(), d(), r(), n()>);
+[[maybe_unused]] static void *resident_fn(uint32_t nterms, bool dur, bool range, bool ntl, bool tf) {
+  return with_shape(nterms, dur, range, ntl, tf, [](auto nt, auto d, auto r, auto n, auto t) {
+    return reinterpret_cast<void *>(search_resident_kernel<nt(), d(), r(), n(), t()>);
   });
 }
 // the device symbol of a kernel instance (Itanium mangling of the template)
-static std::string kernel_symbol(Kernel kind, uint32_t nterms, bool dur, bool range, bool ntl) {
+static std::string kernel_symbol(Kernel kind, uint32_t nterms, bool dur, bool range, bool ntl, bool tf) {
   static const char *const name[] = {"18search_pool_kernel", "20search_static_kernel", "22search_resident_kernel"};
   char b[128];
-  std::snprintf(b, sizeof b, "_ZN3tsg%sILi%uELb%dELb%dELb%dEEEvNS_%sE", name[int(kind)], std::min(nterms, 4u), int(dur),
-                int(range), int(ntl), kind == Kernel::resident ? "12ResidentArgs" : "8PoolArgs");
+  std::snprintf(b, sizeof b, "_ZN3tsg%sILi%uELb%dELb%dELb%dELb%dEEEvNS_%sE", name[int(kind)], std::min(nterms, 4u), int(dur),
+                int(range), int(ntl), int(tf && terms_first_shape(nterms, dur, range)),
+                kind == Kernel::resident ? "12ResidentArgs" : "8PoolArgs");
   return b;
 }
 // the argument ranges a query uses (arg_range), as the parts res_post and aql_dispatch copy
@@ -390,6 +402,8 @@ static std::atomic<uint32_t> g_groups{0};
 // 24.2 us in paired runs, profiles/r06_xsplit; TSG_RES_XSPLIT=1 turns it on)
 static std::atomic<bool> g_xsplit{DeviceCtx::env_u32("TSG_RES_XSPLIT", 0, 0, 1) != 0};
 static std::atomic<uint32_t> g_lb_bitmap{DeviceCtx::env_u32("TSG_LB_BITMAP", 2, 0, 2)};
+// "terms_first": 0 off, 1 forced (where the instance exists), 2 auto (the default; TSG_TERMS_FIRST)
+static std::atomic<int> g_terms_first{int(DeviceCtx::env_u32("TSG_TERMS_FIRST", 2, 0, 2))};
 uint32_t debug_groups() { return g_groups.load(std::memory_order_relaxed); }
 uint32_t debug_lb_bitmap() { return g_lb_bitmap.load(std::memory_order_relaxed); }
 bool debug_xsplit() { return g_xsplit.load(std::memory_order_relaxed); }
@@ -401,6 +415,10 @@ int debug_set(const char *name, int64_t value) {
   }
   if (!std::strcmp(name, "groups")) {
     g_groups.store(uint32_t(std::min<int64_t>(4096, std::max<int64_t>(0, value))));
+    return TSG_OK;
+  }
+  if (!std::strcmp(name, "terms_first")) {
+    g_terms_first.store(int(std::min<int64_t>(2, std::max<int64_t>(0, value))));
     return TSG_OK;
   }
   if (!std::strcmp(name, "xsplit")) {
@@ -581,7 +599,7 @@ static uint32_t slot_of(const std::vector<uint32_t> &pos, const SearchOut::Rec &
 template <class Each>
 static void finish_records(SearchOut &out, const std::vector<uint32_t> &pos, const std::vector<ScanSeg> &segs,
                            const std::vector<std::pair<uint32_t, Block *>> &blocks, uint32_t limit, uint64_t total,
-                           uint32_t W, bool has_dur, bool has_range, Each &&each) {
+                           uint32_t W, bool has_dur, bool has_range, bool terms_first, Each &&each) {
   thread_local std::vector<uint64_t> per;
   per.assign(segs.size(), 0);
   out.recs.resize(total);
@@ -605,7 +623,10 @@ static void finish_records(SearchOut &out, const std::vector<uint32_t> &pos, con
   out.scan_bytes += uint64_t(W) * 4 + kept * 32;  // + workgroup counts, + id/start/end of each record
   // (the caller counted 4 B of duration + 8 B of start / end per entry; these kernels read
   // the one 4 B packed scan word (ds_word.hpp) when either filter is on)
-  const uint64_t counted = (has_dur ? 4u : 0u) + (has_range ? 8u : 0u), read = counted ? 4u : 0u;
+  // terms first: the term bytes only. The scan words (and the exact columns behind them) that the
+  // lanes holding a term-passing entry load, 16 B per lane and step, are not counted: they are rare
+  // where this mode is chosen, and their number is the data's, not the plan's.
+  const uint64_t counted = (has_dur ? 4u : 0u) + (has_range ? 8u : 0u), read = counted && !terms_first ? 4u : 0u;
   for (const auto &sg : segs) out.scan_bytes -= (counted - read) * (sg.n - sg.e0);
 }
 
@@ -615,9 +636,9 @@ static void finish_records(SearchOut &out, const std::vector<uint32_t> &pos, con
 // launch serves them back to back.
 static int resident_search(DeviceCtx &dc, std::unique_lock<std::mutex> &lk, PoolArgs &PA,
                            const std::vector<ScanSeg> &segs, const std::vector<std::pair<uint32_t, Block *>> &blocks,
-                           const tsg_query &q, uint32_t limit, uint32_t flags, bool has_dur, uint32_t threads,
+                           const tsg_query &q, uint32_t limit, uint32_t flags, bool has_dur, bool tf, uint32_t threads,
                            uint32_t W, uint32_t rec_cap, Tracer &tr, SearchOut &out) {
-  const std::string sym = kernel_symbol(Kernel::resident, q.nterms, has_dur, q.has_range, dc.pool_nt);
+  const std::string sym = kernel_symbol(Kernel::resident, q.nterms, has_dur, q.has_range, dc.pool_nt, tf);
   const uint32_t U = PA.units;
   res_split(dc, PA, U, W);
   if (res_max_run(PA, U, W) > kResMaxUnits) return -1;
@@ -697,6 +718,7 @@ static int resident_search(DeviceCtx &dc, std::unique_lock<std::mutex> &lk, Pool
     dc.res_inflight[rel.seq] = uint32_t(ai);
     res_post(dc, rel.seq, kResSearch, &PA, &parts);
     dc.res_queries++;
+    if (tf) dc.tf_queries++;
   };
   // every workgroup's count (stored after its records), with dc.mu released; a launch that ended
   // first (it left on an idle timeout just as this query was posted) is launched again from the
@@ -854,7 +876,7 @@ static int resident_search(DeviceCtx &dc, std::unique_lock<std::mutex> &lk, Pool
   // wave's matches in scan order); a limit keeps each block part's first L
   const uint32_t seg = PA.seg_cap;
   const auto *prec = reinterpret_cast<const SearchOut::Rec *>(recs);
-  finish_records(out, block_slots(segs), segs, blocks, limit, total, W, has_dur, q.has_range != 0, [&](auto &&f) {
+  finish_records(out, block_slots(segs), segs, blocks, limit, total, W, has_dur, q.has_range != 0, tf, [&](auto &&f) {
     for (uint32_t w = 0; w < W; w++) {
       const SearchOut::Rec *r = prec + uint64_t(w) * seg;
       for (uint32_t i = 0, c = counts[size_t(w) * cs]; i < c; i++) f(r[i]);
@@ -862,6 +884,38 @@ static int resident_search(DeviceCtx &dc, std::unique_lock<std::mutex> &lk, Pool
   });
   tr.mark("post");
   return 1;
+}
+
+// Terms first or not for this launch (terms_first.hpp): the shapes without the instance never;
+// "terms_first" 0 / 1 as told; auto from the blocks' per-set counts and the terms' bitmaps, off
+// when a block has no counts, and off for a launch of fewer than kTermsFirstMinUnits units per
+// workgroup (a limit query's first waves, a small block): with its 12 or 16 waves a workgroup then
+// holds at most a unit per wave, the launch's time is latencies in a row and not bytes, and the
+// gated load adds one more behind the term columns' (the crossover was measured on 76 units per
+// workgroup; the limit-20 leg, 2 units per workgroup, was 0.3 us slower with the mode on).
+constexpr uint32_t kTermsFirstMinUnits = 8;
+static bool terms_first_choice(const tsg_query &q, bool has_dur, const std::vector<ScanSeg> &segs,
+                               const std::vector<NarrowSeg> &nsegv, const std::vector<std::array<uint32_t, 8>> &nbms,
+                               const std::vector<std::array<uint8_t, kArgTerms>> &nbmi, uint32_t U, uint32_t W) {
+  if (!terms_first_shape(q.nterms, has_dur, q.has_range != 0)) return false;
+  const int mode = g_terms_first.load(std::memory_order_relaxed);
+  if (mode != 2) return mode == 1;
+  if (uint64_t(U) < uint64_t(kTermsFirstMinUnits) * W) return false;
+  thread_local std::vector<TermsFirstBlock> tb;
+  tb.assign(segs.size(), TermsFirstBlock{});
+  for (size_t i = 0; i < segs.size(); i++) {
+    TermsFirstBlock &b = tb[i];
+    b.entries = nsegv[i].nall;
+    b.scanned = segs[i].n - segs[i].e0;
+    b.nterms = std::min<uint32_t>(q.nterms, 4);
+    for (uint32_t t = 0; t < b.nterms; t++) {
+      const std::vector<uint32_t> *c = nsegv[i].cnt[t];
+      b.counts[t] = c ? c->data() : nullptr;
+      b.ncounts[t] = c ? uint32_t(c->size()) : 0u;
+      b.bitmap[t] = nbms[nbmi[i][t]].data();
+    }
+  }
+  return terms_first_pick(2, terms_first_p(tb.data(), tb.size()));
 }
 
 // One search_pool_kernel launch for a narrow search (every block scanned whole; a limit
@@ -908,6 +962,18 @@ bool pool_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>> 
     U += uint32_t(u);
   }
   PA.ubase[nsegs] = U;
+  bool tf = terms_first_choice(q, has_dur, segs, nsegv, nbms, nbmi, U, W);
+  // A live resident launch of this shape's other instance: leaving it costs a quit and a launch,
+  // far more than the mode saves a query, and queries of both kinds may alternate (a batch of
+  // different conjunctions). Off is taken at once (a block without counts, an unselective
+  // conjunction: the default instance is never wrong by much); terms first only once
+  // kTermsFirstSwitch queries in a row have asked for it. Forced modes are obeyed as they are.
+  if (g_terms_first.load(std::memory_order_relaxed) == 2 && terms_first_shape(q.nterms, has_dur, q.has_range != 0)) {
+    constexpr uint32_t kTermsFirstSwitch = 8;
+    const bool live_off = dc.res_alive && dc.res_kernel == kernel_symbol(Kernel::resident, q.nterms, has_dur, q.has_range, dc.pool_nt, false);
+    if (!tf) dc.tf_streak = 0;
+    else if (live_off && ++dc.tf_streak < kTermsFirstSwitch) tf = false;
+  }
   for (size_t j = 0; j < nbms.size(); j++)
     for (int x = 0; x < 8; x++) PA.bms[j][x] = nbms[j][size_t(x)];
   // static runs: (100 - dyn)% of the units split evenly; the rest in dynamic chunks
@@ -957,7 +1023,7 @@ bool pool_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>> 
   }
   const bool use_static = uint64_t(U) < uint64_t(dc.pool_static_units) * W;
   const Kernel kind = use_static ? Kernel::stat : Kernel::pool;
-  const PoolFn fn = pool_fn(kind, q.nterms, has_dur, q.has_range, dc.pool_nt);
+  const PoolFn fn = pool_fn(kind, q.nterms, has_dur, q.has_range, dc.pool_nt, tf);
   if (!dc.pool_attr.count(reinterpret_cast<const void *>(fn))) {
     HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void *>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                                int(kPoolLds)));
@@ -978,7 +1044,7 @@ bool pool_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>> 
   if (dc.res_on && dc.aql && !want_stamps && !time_scan && (U + W - 1) / W <= kResMaxUnits &&
       contexts_on(dc.ordinal) == 1) {
     if (cotenant_others(dc) == 0) {
-      const int r = resident_search(dc, lk, PA, segs, blocks, q, limit, flags, has_dur, kResThreads, W, rec_cap, tr, out);
+      const int r = resident_search(dc, lk, PA, segs, blocks, q, limit, flags, has_dur, tf, kResThreads, W, rec_cap, tr, out);
       if (r >= 0) return r == 1;
     } else {
       dc.res_cotenant_queries++;
@@ -1015,7 +1081,7 @@ bool pool_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>> 
     // dispatch timestamps, as the untimed ones run); explicit per-call timing stays on HIP events
     const bool aql_timed = first && defer && !time_scan;
     if ((!timed || aql_timed) && !want_stamps && dc.aql)
-      ak = aql_kernel(dc.aql, kernel_symbol(kind, q.nterms, has_dur, q.has_range, dc.pool_nt).c_str(),
+      ak = aql_kernel(dc.aql, kernel_symbol(kind, q.nterms, has_dur, q.has_range, dc.pool_nt, tf).c_str(),
                       uint32_t(sizeof(PoolArgs)));
     if (ak.kobj) {
       // our own AQL packet (aql.hpp): only the argument words this launch's kernel reads
@@ -1034,6 +1100,7 @@ bool pool_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>> 
     }
     if (first && time_all) HIP_OK(hipEventRecord(dc.ev1, s));
     if (!use_static) dc.pool_parity ^= 1u;  // (the static kernel claims nothing)
+    if (tf) dc.tf_queries++;
   };
   // completion: every workgroup's count (stored after its records completed, read with
   // acquire loads); finished segments are pulled into this core's caches meanwhile; the
@@ -1173,7 +1240,7 @@ bool pool_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>> 
   }
   // (the sorted records of a block are contiguous)
   tr.mark("post.sort");
-  finish_records(out, pos, segs, blocks, limit, total, W, has_dur, q.has_range != 0, [&](auto &&f) {
+  finish_records(out, pos, segs, blocks, limit, total, W, has_dur, q.has_range != 0, tf, [&](auto &&f) {
     for (uint64_t i = 0; i < total; i++) f(prec[sorted[i] & 0xfffffu]);
   });
   tr.mark("post");

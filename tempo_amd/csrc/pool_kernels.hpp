@@ -155,16 +155,29 @@ __device__ __forceinline__ uint32_t stream1(const uint8_t *p, uint64_t e) {
   else return *G<uint32_t>(p + e);
 }
 
+// Terms first (TF, a compile-time mode of load_unit and unit_mask and through them of the three
+// kernels; instantiated where it means something: kTermsFirstShape): the packed scan word is 4 of a
+// unit's 7 bytes per entry, and the result needs it only for an entry that has passed every term.
+// A unit's loads are then the term columns alone, and a lane reads its 16 bytes of `ds` for a step
+// only when one of its four entries of that step passed the terms (unit_mask). Which mode a query
+// runs in is the host's choice per launch, from counted selectivities (terms_first.hpp): with a
+// conjunction that passes 1 entry in 8000 a 64-byte line of `ds` holds a passing entry 0.2 % of
+// the time; with one that passes 1 in 50 nearly every step would take the gated load, which waits
+// for everything the wave has in flight.
+template <int NT, bool DUR, bool RANGE>
+constexpr bool kTermsFirstShape = NT > 0 && (DUR || RANGE);
+
 // The loads of the unit at entry e0 of a block (scan columns of npad entries each; cols(q): the
 // block's q-th term column, read when its loads are issued). Wave-uniform arguments.
-template <int NT, bool DUR, bool RANGE, bool NTL, class Cols>
+template <int NT, bool DUR, bool RANGE, bool NTL, bool TF, class Cols>
 __device__ __forceinline__ void load_unit(UnitRegs<NT> &R, const uint32_t *scan, uint32_t npad, Cols &&cols,
                                           uint32_t e0, int lane) {
+  static_assert(!TF || kTermsFirstShape<NT, DUR, RANGE>, "terms first: a term and a filter on the scan word");
   R.e0 = e0;
 #pragma unroll
   for (int k = 0; k < kSteps; k++) {
     const uint64_t e = uint64_t(e0) + uint64_t(k) * 256 + uint64_t(lane) * 4;
-    if (DUR || RANGE) R.d[k] = stream4<NTL>(scan + 3ull * npad, e);
+    if ((DUR || RANGE) && !TF) R.d[k] = stream4<NTL>(scan + 3ull * npad, e);
   }
 #pragma unroll
   for (int q = 0; q < (NT > 0 ? NT : 1); q++) {
@@ -255,21 +268,43 @@ __device__ __forceinline__ UnitPred<NT> unit_pred(uint32_t dlo, uint32_t dhi, ui
   for (int q = 0; q < (NT > 0 ? NT : 1); q++) P.tb[q] = ((bmi4 >> (8 * q)) & 0xffu) * 256u;
   return P;
 }
-template <int NT, bool DUR, bool RANGE, bool NTL>
+// The range verdicts of a lane's four words of a step from ds_word.hpp's decode (the escape path
+// above): bit j = entry j lies in the query's range.
+template <bool NTL>
+__device__ __forceinline__ uint32_t range_decode_nib(const uint32_t (&w)[4], bool esc_s, bool esc_e, uint32_t start_s,
+                                                     uint32_t end_s, uint32_t sbase, const uint32_t *scan, uint32_t npad,
+                                                     uint64_t e) {
+  // req.Start <= endSeconds && req.End >= startSeconds (pipeline.go:62-63)
+  u32x4 sv = {ds_start(w[0], sbase), ds_start(w[1], sbase), ds_start(w[2], sbase), ds_start(w[3], sbase)};
+  if (esc_s) sv = stream4<NTL>(scan + npad, e);
+  u32x4 ev = {ds_end(w[0], sv.x), ds_end(w[1], sv.y), ds_end(w[2], sv.z), ds_end(w[3], sv.w)};
+  if (esc_e) ev = stream4<NTL>(scan + 2ull * npad, e);
+  return uint32_t((start_s <= ev.x) & (end_s >= sv.x)) | uint32_t((start_s <= ev.y) & (end_s >= sv.y)) << 1 |
+         uint32_t((start_s <= ev.z) & (end_s >= sv.z)) << 2 | uint32_t((start_s <= ev.w) & (end_s >= sv.w)) << 3;
+}
+// Terms first: a step's nib is formed from the byte-table term tests alone; a lane whose nib is not
+// zero (the same kind of per-lane branch as the escape reloads': the other lanes wait for it) loads
+// its 16 bytes of `ds` for the step, applies the duration and range tests to them, and runs the
+// escape path behind them as it is. The verdicts are the same bits in the same order: an entry's
+// bit is the and of its tests either way, and a zero nib stays zero. The gated load is waited for
+// at once, which drains what the wave has in flight, as an escape reload does: the host chooses this
+// mode only where few steps hold a term-passing entry.
+template <int NT, bool DUR, bool RANGE, bool NTL, bool TF>
 __device__ __forceinline__ uint32_t unit_mask(const UnitRegs<NT> &R, const UnitPred<NT> &P, const uint8_t *s_tb,
                                               const uint32_t *scan, uint32_t npad, int lane) {
   uint32_t mask = 0;
 #pragma unroll
   for (int k = kSteps - 1; k >= 0; k--) {
+    const uint64_t e = uint64_t(R.e0) + uint64_t(k) * 256 + uint64_t(lane) * 4;
     uint32_t w[4] = {0, 0, 0, 0};
-    if (DUR || RANGE) {
+    if ((DUR || RANGE) && !TF) {
       w[0] = R.d[k].x;
       w[1] = R.d[k].y;
       w[2] = R.d[k].z;
       w[3] = R.d[k].w;
     }
     bool esc_s = false, esc_e = false, slow = false;
-    if (RANGE) {
+    if (RANGE && !TF) {
       esc_s = ds_any_start_escaped(w[0], w[1], w[2], w[3]);
       esc_e = ds_any_end_escaped(w[0], w[1], w[2], w[3]);
       slow = esc_s | esc_e | !P.rng.fast;
@@ -278,8 +313,8 @@ __device__ __forceinline__ uint32_t unit_mask(const UnitRegs<NT> &R, const UnitP
 #pragma unroll
     for (int j = 3; j >= 0; j--) {
       bool ok = true;
-      if (DUR) ok = ds_dur_ok(w[j], P.dur);
-      if (RANGE) ok = ok & (slow | ds_range_ok(w[j], P.rng.e_lim, P.rng.s_lim));
+      if (DUR && !TF) ok = ds_dur_ok(w[j], P.dur);
+      if (RANGE && !TF) ok = ok & (slow | ds_range_ok(w[j], P.rng.e_lim, P.rng.s_lim));
       if (NT > 0) {
         uint32_t hits = 0;
 #pragma unroll
@@ -288,20 +323,34 @@ __device__ __forceinline__ uint32_t unit_mask(const UnitRegs<NT> &R, const UnitP
       }
       nib = nib + nib + uint32_t(ok);
     }
-    // (only a lane that can still match: the terms, the duration and, where the word's tests hold,
-    // the range are in nib already, and nib &= in leaves a zero nib as it is)
-    if (RANGE && slow && nib != 0) {
-      // req.Start <= endSeconds && req.End >= startSeconds (pipeline.go:62-63)
-      const uint64_t e = uint64_t(R.e0) + uint64_t(k) * 256 + uint64_t(lane) * 4;
-      u32x4 sv = {ds_start(w[0], P.sbase), ds_start(w[1], P.sbase), ds_start(w[2], P.sbase), ds_start(w[3], P.sbase)};
-      if (esc_s) sv = stream4<NTL>(scan + npad, e);
-      u32x4 ev = {ds_end(w[0], sv.x), ds_end(w[1], sv.y), ds_end(w[2], sv.z), ds_end(w[3], sv.w)};
-      if (esc_e) ev = stream4<NTL>(scan + 2ull * npad, e);
-      const uint32_t in = uint32_t((P.start_s <= ev.x) & (P.end_s >= sv.x)) |
-                          uint32_t((P.start_s <= ev.y) & (P.end_s >= sv.y)) << 1 |
-                          uint32_t((P.start_s <= ev.z) & (P.end_s >= sv.z)) << 2 |
-                          uint32_t((P.start_s <= ev.w) & (P.end_s >= sv.w)) << 3;
-      nib &= in;
+    if constexpr (TF) {
+      if (nib != 0) {
+        const u32x4 d = stream4<NTL>(scan + 3ull * npad, e);
+        w[0] = d.x;
+        w[1] = d.y;
+        w[2] = d.z;
+        w[3] = d.w;
+        if (RANGE) {
+          esc_s = ds_any_start_escaped(w[0], w[1], w[2], w[3]);
+          esc_e = ds_any_end_escaped(w[0], w[1], w[2], w[3]);
+          slow = esc_s | esc_e | !P.rng.fast;
+        }
+        uint32_t fn = 0;
+#pragma unroll
+        for (int j = 3; j >= 0; j--) {
+          bool ok = true;
+          if (DUR) ok = ds_dur_ok(w[j], P.dur);
+          if (RANGE) ok = ok & (slow | ds_range_ok(w[j], P.rng.e_lim, P.rng.s_lim));
+          fn = fn + fn + uint32_t(ok);
+        }
+        nib &= fn;
+        if (RANGE && slow && nib != 0)
+          nib &= range_decode_nib<NTL>(w, esc_s, esc_e, P.start_s, P.end_s, P.sbase, scan, npad, e);
+      }
+    } else if (RANGE && slow && nib != 0) {
+      // (only a lane that can still match: the terms, the duration and, where the word's tests hold,
+      // the range are in nib already, and nib &= in leaves a zero nib as it is)
+      nib &= range_decode_nib<NTL>(w, esc_s, esc_e, P.start_s, P.end_s, P.sbase, scan, npad, e);
     }
     mask = (mask << 4) | nib;
   }
@@ -424,7 +473,7 @@ __device__ __forceinline__ void hand_off_segment(const PoolArgs &A, const unsign
 }
 
 // ------------------------------------------------------------------------------------
-template <int NT, bool DUR, bool RANGE, bool NTL>
+template <int NT, bool DUR, bool RANGE, bool NTL, bool TF>
 __global__ void __launch_bounds__(kPoolThreads, 1) search_pool_kernel(PoolArgs A) {
   const unsigned long long t_start = A.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;
   __shared__ __attribute__((aligned(16))) PoolBlk s_blk[kArgSegs];
@@ -450,7 +499,7 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_pool_kernel(PoolArgs A
     while (b + 1 < nsegs && u >= A.ubase[b + 1]) b++;
     R.blk = b;
     const PoolBlk &B = A.blk[b];
-    load_unit<NT, DUR, RANGE, NTL>(R, B.scan, B.npad, [&](int q) { return B.col[q]; },
+    load_unit<NT, DUR, RANGE, NTL, TF>(R, B.scan, B.npad, [&](int q) { return B.col[q]; },
                                    A.ebase[b] + (u - A.ubase[b]) * kPoolTile, lane);
   };
   // the staging's kernel-argument words first, by vector loads issued ahead of the units'
@@ -551,13 +600,13 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_pool_kernel(PoolArgs A
     const PoolBlk &B = s_blk[b];
     const uint32_t npad = rfl(B.npad);
     const uint32_t *scan = uniform_ptr(B.scan);
-    load_unit<NT, DUR, RANGE, NTL>(R, scan, npad, [&](int q) { return uniform_ptr(B.col[q]); },
+    load_unit<NT, DUR, RANGE, NTL, TF>(R, scan, npad, [&](int q) { return uniform_ptr(B.col[q]); },
                                    rfl(A.ebase[b]) + (u - rfl(B.ubase)) * kPoolTile, lane);
   };
   auto eval = [&](const Unit &R) {
     const PoolBlk &B = s_blk[R.blk];
     const UnitPred<NT> P = unit_pred<NT>(dlo, dhi, A.start_s, A.end_s, rfl(s_sb[R.blk]), rfl(B.nent), rfl(B.bmi4));
-    uint32_t mask = unit_mask<NT, DUR, RANGE, NTL>(R, P, s_tb, uniform_ptr(B.scan), rfl(B.npad), lane);
+    uint32_t mask = unit_mask<NT, DUR, RANGE, NTL, TF>(R, P, s_tb, uniform_ptr(B.scan), rfl(B.npad), lane);
     if (__ballot(mask != 0) == 0) return;
     if (A.unit_cap) mask = cap_unit_mask(mask, A.unit_cap, lane);
     put_unit(s_rec, &s_nrec, rec_cap, mask, A.desc[R.blk], rfl(B.block_idx), R.e0, lane);
@@ -599,7 +648,7 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_pool_kernel(PoolArgs A
 // from LDS: the first loads are issued before anything is staged, and nothing is claimed.
 // (scan_probe.hip measured this shape at 27.0 us for 150 MB against 32.4 us for the pool
 // kernel with its LDS claims, staging and dynamic chunks.)
-template <int NT, bool DUR, bool RANGE, bool NTL>
+template <int NT, bool DUR, bool RANGE, bool NTL, bool TF>
 __global__ void __launch_bounds__(kPoolThreads, 1) search_static_kernel(PoolArgs A) {
   const unsigned long long t_start = A.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;
   __shared__ __attribute__((aligned(16))) uint8_t s_tb[kArgBms * 256];  // the terms' byte tables
@@ -641,7 +690,7 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_static_kernel(PoolArgs
       while (b + 1 < nsegs && u >= A.ubase[b + 1]) b++;
       set_block(b);
     }
-    load_unit<NT, DUR, RANGE, NTL>(R, B.scan, B.npad, [&](int q) { return B.col[q]; },
+    load_unit<NT, DUR, RANGE, NTL, TF>(R, B.scan, B.npad, [&](int q) { return B.col[q]; },
                                    B.eb + (u - B.ub) * kPoolTile, lane);
   };
   const uint32_t rec_cap = A.rec_cap;
@@ -650,7 +699,7 @@ __global__ void __launch_bounds__(kPoolThreads, 1) search_static_kernel(PoolArgs
   auto eval = [&](const Unit &R, uint32_t bslot) {
     const PoolBlk &P = A.blk[bslot];
     const UnitPred<NT> U = unit_pred<NT>(dlo, dhi, A.start_s, A.end_s, A.sbase[bslot], P.nent, P.bmi4);
-    uint32_t mask = unit_mask<NT, DUR, RANGE, NTL>(R, U, s_tb, P.scan, P.npad, lane);
+    uint32_t mask = unit_mask<NT, DUR, RANGE, NTL, TF>(R, U, s_tb, P.scan, P.npad, lane);
     if (__ballot(mask != 0) == 0) return;
     if (A.unit_cap) mask = cap_unit_mask(mask, A.unit_cap, lane);
     put_unit(s_rec, &s_nrec, rec_cap, mask, A.desc[bslot], P.block_idx, R.e0, lane);
@@ -764,7 +813,7 @@ static_assert(sizeof(PoolArgs) <= kResSlotBytes - kResHdrBytes && sizeof(PoolArg
 // latency (config 2: 34 MB in flight)
 constexpr uint32_t kResWaves = 12, kResThreads = kResWaves * 64;
 constexpr uint32_t kResMaxRecs = uint32_t(kPoolLds / sizeof(MatchRec));  // the LDS record buffer
-template <int NT, bool DUR, bool RANGE, bool NTL>
+template <int NT, bool DUR, bool RANGE, bool NTL, bool TF>
 __global__ void __launch_bounds__(kResThreads, 1) search_resident_kernel(ResidentArgs R) {
   __shared__ __attribute__((aligned(16))) uint32_t s_args[sizeof(PoolArgs) / 4];
   __shared__ __attribute__((aligned(16))) uint8_t s_tb[kArgBms * 256];  // the terms' byte tables
@@ -928,7 +977,7 @@ __global__ void __launch_bounds__(kResThreads, 1) search_resident_kernel(Residen
       const uint32_t *scan = uniform_ptr(P.scan);
       const uint32_t npad = rfl(P.npad);
       Rg.k = k;
-      load_unit<NT, DUR, RANGE, NTL>(Rg, scan, npad, [&](int q) { return uniform_ptr(P.col[q]); },
+      load_unit<NT, DUR, RANGE, NTL, TF>(Rg, scan, npad, [&](int q) { return uniform_ptr(P.col[q]); },
                                      rfl(A.ebase[b]) + (u - rfl(A.ubase[b])) * kPoolTile, lane);
     };
     // the unit's matches into the LDS buffer in scan order (k-step, lane, j), in two halves:
@@ -951,7 +1000,7 @@ __global__ void __launch_bounds__(kResThreads, 1) search_resident_kernel(Residen
       const uint32_t blk = block_of(A.ubase, nsegs, ua + Rg.k, lane);
       const PoolBlk &P = A.blk[blk];
       const UnitPred<NT> U = unit_pred<NT>(dlo, dhi, start_s, end_s, rfl(A.sbase[blk]), rfl(P.nent), rfl(P.bmi4));
-      uint32_t mask = unit_mask<NT, DUR, RANGE, NTL>(Rg, U, s_tb, uniform_ptr(P.scan), rfl(P.npad), lane);
+      uint32_t mask = unit_mask<NT, DUR, RANGE, NTL, TF>(Rg, U, s_tb, uniform_ptr(P.scan), rfl(P.npad), lane);
       if (__ballot(mask != 0) == 0) return;
       if (ucap) mask = cap_unit_mask(mask, ucap, lane);
       uint32_t cnt = uint32_t(__popc(mask));

@@ -2048,6 +2048,7 @@ void device_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>
       ns.ncol = d.narrow_base;
       ns.npad = uint32_t(d.npad);
       ns.sbase = d.sbase;
+      ns.nall = d.n;
       for (uint32_t t = 0; t < q.nterms && all_narrow; t++) {
         const size_t k = size_t(kidx[t]);
         if (d.narrow_slot.size() <= k || d.narrow_slot[k] < 0 || d.narrow_slot[k] > 255 || !b.narrow[k]) {
@@ -2057,6 +2058,8 @@ void device_search(DeviceCtx &dc, const std::vector<std::pair<uint32_t, Block *>
         ns.slot[t] = uint8_t(d.narrow_slot[k]);
         ns.nsets[t] = uint8_t(d.keys[k].nsets);
         ns.dict[t] = b.narrow[k].get();
+        const auto &sc = b.host->keys[k].set_count;  // (counted at load; none: a refreshed WAL block)
+        ns.cnt[t] = sc.size() == d.keys[k].nsets ? &sc : nullptr;
       }
       if (d.npad >= (1ull << 32)) all_narrow = false;
       nsegv.push_back(ns);

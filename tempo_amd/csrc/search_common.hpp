@@ -148,6 +148,10 @@ struct NarrowSeg {
   uint32_t sbase;  // the block's base second of its packed scan words (ds_word.hpp)
   std::array<uint8_t, kArgTerms> slot, nsets;
   std::array<const NarrowDict *, kArgTerms> dict;
+  // per term: the key's per-set entry counts (KeyColumn::set_count; nullptr: the block has none)
+  // over the block's `nall` entries: the terms-first choice (pool.hip)
+  std::array<const std::vector<uint32_t> *, kArgTerms> cnt;
+  uint64_t nall;
 };
 
 void print_stamps(DeviceCtx &dc, uint32_t nwg, bool fast);

@@ -731,9 +731,10 @@ class Engine:
         """tsg_device_counters: the resident search kernel's launches, queries served, relaunches
         (a launch that left on its idle timeout as a query was posted), quits, slot reads the
         kernel rejected (check mismatch), narrow queries launched plainly because another process
-        has a context on the GPU, narrow queries launched plainly (any reason), XCD-split samples."""
+        has a context on the GPU, narrow queries launched plainly (any reason), XCD-split samples, narrow
+        queries served by a terms-first kernel instance (resident or plain launches)."""
         keys = ("launches", "queries", "relaunches", "quits", "rejects", "cotenant_queries", "plain_queries",
-                "xsplit_samples")
+                "xsplit_samples", "terms_first_queries")
         buf = (C.c_uint64 * len(keys))()
         _check(lib().tsg_device_counters(self.h, dev, buf, len(keys)))
         return dict(zip(keys, list(buf)))
