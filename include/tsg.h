@@ -212,7 +212,8 @@ int tsg_device_numa_node(tsg_ctx *ctx, int dev);
  * another process has a libtsg context on the same GPU, [6] narrow queries launched plainly
  * (any reason), [7] samples taken for the XCD-weighted split. Zeros when TSG_RESIDENT=0.
  * [8] narrow queries served by a terms-first kernel instance (resident or plain launches).
- * DESIGN.md §4. */
+ * DESIGN.md §4. [9] bytes tsg_find_ids read from the data files of TSG_V2_DATA_ON_DEMAND blocks,
+ * [10] the find rounds it ran (one per call unless the staging cap cut the batch). */
 int tsg_device_counters(tsg_ctx *ctx, int dev, uint64_t *out, size_t n);
 const char *tsg_last_error(void);
 int tsg_abi_version(void);
@@ -400,7 +401,8 @@ int tsg_search_batch(tsg_ctx *ctx, const tsg_search_item *items, size_t n, uint3
  * matched as one byte stream (0 = the default, 1 MiB); a query with a term that streams only
  * because of the hook takes the dictionary-pass path. "dict_stream_span" = b: every wave of the
  * stream kernel owns b bytes, a multiple of 1024 from 1024 to 65536 (0 = the planned span;
- * TSG_E_INVALID for another value). TSG_E_INVALID for an unknown name.
+ * TSG_E_INVALID for another value). "find_stage_bytes" = n: the staging cap of tsg_find_ids over
+ * TSG_V2_DATA_ON_DEMAND blocks (0 = TSG_FIND_STAGE_BYTES or 256 MiB). TSG_E_INVALID for an unknown name.
  * tsg_debug_get reads a process-wide counter: "dict_stream_jobs" / "dict_lane_jobs" = the
  * (block, term) dictionary jobs of dictionary-pass searches that the stream kernel / the
  * lane-per-value kernel ran so far. TSG_E_INVALID for an unknown name or a NULL out. */
@@ -474,6 +476,18 @@ int tsg_shm_merge(tsg_shm *s, uint32_t seq, uint64_t limit, uint64_t total_block
 /* ---- v2 trace blocks: batched trace-ID lookup --------------------------------- */
 /* Reads <block_dir>/{meta.json,bloom-N...,index}; verifies index page checksums. */
 int tsg_v2block_open(tsg_ctx *ctx, const char *block_dir, int device_hint, tsg_v2block **out);
+/* The same open with a choice of where <block_dir>/data lives between calls.
+ * TSG_V2_DATA_RESIDENT: the whole file is copied to the device at the open (tsg_v2block_open;
+ * TSG_V2_NO_DATA=1 in the environment skips it, and every hit of tsg_find_ids then reports
+ * TSG_E_UNSUPPORTED). TSG_V2_DATA_ON_DEMAND: nothing of the file goes to the device; the block
+ * holds a read-only descriptor of it (closed by tsg_v2block_close) and its length at the open,
+ * and tsg_find_ids reads exactly the pages its hits name, per call (below). The file may be
+ * renamed or unlinked meanwhile. A missing data file opens in both modes (its hits report
+ * TSG_E_UNSUPPORTED). Another data_mode -> TSG_E_INVALID. */
+#define TSG_V2_DATA_RESIDENT 0u
+#define TSG_V2_DATA_ON_DEMAND 1u
+int tsg_v2block_open_mode(tsg_ctx *ctx, const char *block_dir, int device_hint, uint32_t data_mode,
+                          tsg_v2block **out);
 void tsg_v2block_close(tsg_v2block *b);
 
 typedef struct tsg_lookup_opts {
@@ -514,7 +528,20 @@ void tsg_lookup_result_free(tsg_lookup_result *r);
  * objects are scanned for the exact id. One entry per lookup hit, sorted (id_idx,
  * block_idx): status TSG_OK with the object's bytes (what findOne returns), TSG_E_NOT_FOUND
  * (a bloom false positive: findOne returns nil), or the error findOne returns for that
- * page (read, framing, decompression, object framing). */
+ * page (read, framing, decompression, object framing).
+ * Pages of a TSG_V2_DATA_ON_DEMAND block are read from its data file (pread, at most 8 host
+ * threads) into pinned memory and copied to a staging buffer on the device that calls reuse; the
+ * kernels then run on them as on resident pages, and the results are the resident mode's bit for
+ * bit. A record that ends past the file's length at the open, a short read and a read error give
+ * that page's hits TSG_E_CORRUPT (the read's errno text in tsg_last_error) and leave other pages
+ * alone. The staged bytes of a call are bounded by a cap (256 MiB; TSG_FIND_STAGE_BYTES in the
+ * environment; tsg_debug_set("find_stage_bytes", n), 0 = the default): a batch whose on-demand
+ * pages exceed it runs as consecutive rounds, each a maximal run of pages (in block, record order)
+ * that fits, the next round's pages read while this one's kernels run; a page longer than the cap
+ * is a round of its own. The decode arena is sized per round too. Resident and on-demand blocks
+ * mix freely in one call. kernel_ns is the sum of the rounds' device time (the staging copies
+ * included, the file reads not). tsg_device_counters [9] and [10] count the bytes read and the
+ * rounds run. */
 typedef struct tsg_find_result {
   uint64_t n;
   const uint32_t *id_idx;

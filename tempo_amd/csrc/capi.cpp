@@ -29,6 +29,7 @@
 #include "block.hpp"
 #include "common.hpp"
 #include "engine.hpp"
+#include "find_rounds.hpp"
 #include "park.hpp"
 #include "proto.hpp"
 #include "writer.hpp"
@@ -764,9 +765,9 @@ int tsg_device_numa_node(tsg_ctx *ctx, int dev) {
 int tsg_device_counters(tsg_ctx *ctx, int dev, uint64_t *out, size_t n) {
   if (!ctx || !out || dev < 0 || size_t(dev) >= ctx->c.devs.size()) return TSG_E_INVALID;
   return guard([&] {
-    uint64_t c[9];
+    uint64_t c[kDeviceCounters] = {};
     device_counters(*ctx->c.devs[size_t(dev)], c);
-    for (size_t i = 0; i < n; i++) out[i] = i < 9 ? c[i] : 0;
+    for (size_t i = 0; i < n; i++) out[i] = i < kDeviceCounters ? c[i] : 0;
   });
 }
 int tsg_cancel(tsg_ctx *ctx, uint64_t qid) {
@@ -2625,6 +2626,10 @@ int tsg_debug_set(const char *name, int64_t value) {
     zstd_writer_flags(uint32_t(value) & 63u);
     return TSG_OK;
   }
+  if (name && !std::strcmp(name, "find_stage_bytes")) {  // (find_rounds.hpp: the staging cap, 0 = the default)
+    g_find_stage_bytes.store(uint64_t(std::max<int64_t>(0, value)));
+    return TSG_OK;
+  }
   return debug_set(name, value);
 }
 int tsg_debug_get(const char *name, uint64_t *out) {
@@ -2701,9 +2706,14 @@ int tsg_results_combine(const tsg_result *in, uint32_t max_results, tsg_result *
 
 // ---- v2 lookup -----------------------------------------------------------------------
 int tsg_v2block_open(tsg_ctx *ctx, const char *dir, int device_hint, tsg_v2block **out) {
+  return tsg_v2block_open_mode(ctx, dir, device_hint, TSG_V2_DATA_RESIDENT, out);
+}
+int tsg_v2block_open_mode(tsg_ctx *ctx, const char *dir, int device_hint, uint32_t data_mode, tsg_v2block **out) {
   if (!ctx || !dir || !out) return TSG_E_INVALID;
+  if (data_mode != TSG_V2_DATA_RESIDENT && data_mode != TSG_V2_DATA_ON_DEMAND) return TSG_E_INVALID;
   return guard([&] {
     auto *b = new tsg_v2block();
+    b->b.data_mode = data_mode;
     try {
       v2block_open(ctx->c, b->b, dir, device_hint);
     } catch (...) {
@@ -2805,11 +2815,17 @@ int tsg_find_ids(tsg_ctx *ctx, tsg_v2block *const *blocks, size_t nblocks, const
   return guard([&] {
     auto *h = new FindHolder();
     std::unique_ptr<FindHolder> g(h);
+    std::mutex emu;
+    std::string read_error;  // (a device's find may run on another thread: the text is set on this one)
     per_device_merge(ctx, blocks, nblocks, h->o,
                      [&](DeviceCtx &dc, const std::vector<std::pair<uint32_t, V2Block *>> &list, FindOut &o) {
                        device_find(dc, list, ids, nids, opts, o);
+                       if (o.read_error.empty()) return;
+                       std::lock_guard<std::mutex> elk(emu);
+                       read_error = o.read_error;
                      },
                      find_append);
+    if (!read_error.empty()) set_last_error(read_error);
     h->pub.n = h->o.id_idx.size();
     h->pub.id_idx = h->o.id_idx.data();
     h->pub.block_idx = h->o.block_idx.data();

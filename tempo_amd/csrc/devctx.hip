@@ -61,7 +61,7 @@ void pinned_put(void *p, size_t) {
     g_pin_free.erase(it);
   }
 }
-void device_counters(DeviceCtx &dc, uint64_t out[9]) {
+void device_counters(DeviceCtx &dc, uint64_t out[kDeviceCounters]) {
   std::lock_guard<std::mutex> lk(dc.mu);
   out[0] = dc.res_launches;
   out[1] = dc.res_queries;
@@ -72,6 +72,8 @@ void device_counters(DeviceCtx &dc, uint64_t out[9]) {
   out[6] = dc.res_plain_queries;
   out[7] = dc.res_xsamples;
   out[8] = dc.tf_queries;
+  out[9] = dc.find_read_bytes;
+  out[10] = dc.find_rounds;
 }
 
 void ctx_init(Ctx &c, const tsg_options *opts) {
@@ -124,12 +126,14 @@ void ctx_shutdown(Ctx &c) {
     for (DevBuf *b : {&dc->desc, &dc->vmatch, &dc->bitmaps, &dc->gran, &dc->ticket, &dc->out, &dc->regions,
                       &dc->seg_counts, &dc->hdr, &dc->err, &dc->maskbits, &dc->agg, &dc->stamps, &dc->gbm, &dc->lkhits,
                       &dc->done, &dc->steal, &dc->fpages, &dc->fhits, &dc->fres, &dc->farena, &dc->fcrc, &dc->fdst, &dc->foff,
+                      &dc->fstage,
                       &dc->danyf, &dc->pool_head, &dc->lkslab, &dc->lkslabdesc, &dc->pbm, &dc->pout, &dc->pjob})
       b->release();
     for (hipEvent_t e : dc->tring) (void)hipEventDestroy(e);
     dc->hdesc.release();
     dc->hout.release();
     dc->lkstage.release();
+    for (HostBuf &h : dc->fstage_host) h.release();
     for (auto &e : dc->lk_ev)
       if (e) (void)hipEventDestroy(e);
     dc->hres.release();

@@ -101,6 +101,12 @@ struct DeviceCtx {
   DevBuf pbm, pout;  // proto search: term bitmaps, per-object match/error bits
   DevBuf pjob;       // batched proto search: [job table | first-workgroup prefix | term bitmaps]
   DevBuf fpages, fhits, fres, farena, fcrc, fdst, foff;  // device findOne (find.hip)
+  // findOne over blocks whose data file stays on disk: a round's hit pages, read into one of two
+  // pinned buffers (the next round is read while this one's kernels run) and copied to fstage
+  DevBuf fstage;
+  HostBuf fstage_host[2];
+  std::mutex fstage_mu;  // the pinned buffers' lock, taken before mu: round 0 is read before mu is held
+  uint64_t find_read_bytes = 0, find_rounds = 0;  // tsg_device_counters [9], [10]
   HostBuf hdesc, hout;
   // lookup: pinned staging of the caller's (pageable) probe ids, two chunks in turn: the host
   // copies one while the other's DMA runs (lookup.hip upload_ids)

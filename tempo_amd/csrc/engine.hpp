@@ -195,6 +195,11 @@ struct V2Block {
   const uint8_t *d_data = nullptr;
   uint64_t data_len = 0;
   int enc = -1;
+  // data_mode (set before v2block_open) TSG_V2_DATA_ON_DEMAND: nothing of the file on the device;
+  // data_fd is <dir>/data open read-only (-1: no such file), data_len its length at the open, and
+  // device_find reads the hit pages of each call through it (find_rounds.hpp)
+  uint32_t data_mode = 0;
+  int data_fd = -1;
   std::vector<void *> allocs;
 };
 void v2block_open(Ctx &c, V2Block &b, const std::string &dir, int device_hint);
@@ -244,14 +249,17 @@ struct FindOut {
   std::vector<uint32_t> obj_len;
   std::vector<uint8_t> bytes;
   uint64_t kernel_ns = 0;
+  std::string read_error;  // the last failed read of a page from a data file kept on disk (tsg_last_error)
 };
 void device_find(DeviceCtx &dc, const std::vector<std::pair<uint32_t, V2Block *>> &blocks, const uint8_t (*ids)[16],
                  size_t nids, const tsg_lookup_opts *opts, FindOut &out);
 
 int device_ordinal(const DeviceCtx &dc);
 // resident search counters: launches, queries served, relaunches after an idle-exit race, quits,
-// ...; [8] = the narrow queries a terms-first instance served (resident, pool or static kernel)
-void device_counters(DeviceCtx &dc, uint64_t out[9]);
+// ...; [8] = the narrow queries a terms-first instance served (resident, pool or static kernel);
+// [9] = bytes device_find read from data files kept on disk, [10] = the find rounds it ran
+constexpr size_t kDeviceCounters = 11;
+void device_counters(DeviceCtx &dc, uint64_t out[kDeviceCounters]);
 // The last full scan on the device's dictionary-pass path had more than one match per 64
 // entries (search.hip: its next full scans there return bitmaps; tsg_search pipelines them)
 bool device_last_dense(DeviceCtx &dc);

@@ -28,14 +28,21 @@
 // (lz4_dev.hpp parses the frame; find_decode_lz4_kernel: one wave per page, each block
 // decoded through a 64 KiB output ring in LDS, step (3'') below); gzip / s2 report
 // TSG_E_UNSUPPORTED_ENCODING per hit (the caller's CPU path takes those blocks).
+// A block opened with TSG_V2_DATA_ON_DEMAND has no page in HBM: step (1) also plans rounds over
+// its pages (find_rounds.hpp), and each round's pages are read from the data file into pinned
+// memory and copied to dc.fstage before steps (2) to (5) run on them (the host part, below).
 #include <hip/hip_runtime.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
+#include <cerrno>
 #include <cstring>
 #include <numeric>
+#include <thread>
 
 #include "devctx.hpp"
+#include "find_rounds.hpp"
 #include "lz4_dev.hpp"
 #include "snappy_dev.hpp"
 #include "zstd_dev.hpp"
@@ -62,6 +69,7 @@ extern "C" __global__ void __launch_bounds__(256) find_size_kernel(FindPage *pag
   if (i >= npages) return;
   FindPage &P = pages[i];
   P.out_len = 0;
+  if (P.status != TSG_OK) return;  // (the host's verdict: no data file, a record past its end, a failed read)
   // unmarshalPageFromBytes with the data header (length 0) (page.go:28-57)
   if (P.len < 6 || rd32(P.src) != P.len || (uint32_t(P.src[4]) | uint32_t(P.src[5]) << 8) != 0) {
     P.status = TSG_E_CORRUPT;
@@ -550,58 +558,73 @@ static void crc_tables(CrcArgs &c) {
   }
 }
 
-void device_find(DeviceCtx &dc, const std::vector<std::pair<uint32_t, V2Block *>> &blocks, const uint8_t (*ids)[16],
-                 size_t nids, const tsg_lookup_opts *opts, FindOut &out) {
-  LookupOut lk;
-  device_lookup(dc, blocks, ids, nids, opts, lk);
-  out = FindOut();
-  const size_t nh = lk.id_idx.size();
-  out.id_idx.assign(lk.id_idx.begin(), lk.id_idx.end());
-  out.block_idx.assign(lk.block_idx.begin(), lk.block_idx.end());
-  out.status.assign(nh, TSG_E_NOT_FOUND);
-  out.obj_off.assign(nh, 0);
-  out.obj_len.assign(nh, 0);
-  out.kernel_ns = lk.kernel_ns;
-  if (nh == 0) return;
-  std::unordered_map<uint32_t, const V2Block *> by_idx;
-  for (auto &bp : blocks) by_idx[bp.first] = bp.second;
-  // (1) distinct pages, hits grouped by page
-  std::vector<uint32_t> order(nh);
-  std::iota(order.begin(), order.end(), 0u);
-  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
-    return lk.block_idx[a] != lk.block_idx[b] ? lk.block_idx[a] < lk.block_idx[b] : lk.rec[a] < lk.rec[b];
-  });
-  std::vector<FindPage> pages;
-  std::vector<uint8_t> hid(nh * 16, 0);  // ids in page order
-  std::vector<uint32_t> slot(nh);        // page order -> hit
-  for (size_t k = 0; k < nh; k++) {
-    const uint32_t h = order[k];
-    const V2Block *b = by_idx.at(lk.block_idx[h]);
-    if (pages.empty() || k == 0 || lk.block_idx[order[k - 1]] != lk.block_idx[h] || lk.rec[order[k - 1]] != lk.rec[h]) {
-      FindPage pg{};
-      pg.hit0 = uint32_t(k);
-      if (!b->d_data) {
-        pg.status = TSG_E_UNSUPPORTED;  // data file not resident
-      } else if (lk.start[h] + lk.len[h] > b->data_len) {
-        pg.status = TSG_E_CORRUPT;  // ReadAt past the end of the data file
-      } else {
-        pg.src = b->d_data + lk.start[h];
-        pg.len = lk.len[h];
-        pg.enc = uint32_t(b->enc);
-        pg.status = TSG_OK;
+// ---- pages of blocks whose data file stays on disk (TSG_V2_DATA_ON_DEMAND) ---------------------
+// A round's pages (find_rounds.hpp) are read with pread into a pinned buffer by at most
+// kFindReaders threads, each taking the next page not yet taken. The threads of round k + 1
+// run while round k's kernels do.
+constexpr unsigned kFindReaders = 8;
+struct StagePage {
+  int fd;
+  uint64_t start, off;  // in the file, in the staging buffer
+  uint32_t len;
+  uint32_t page;  // index into the batch's pages
+  int err;        // 0, the read's errno, or -1: the file ended inside the page
+};
+struct RoundRead {
+  std::vector<StagePage> pages;
+  uint8_t *dst = nullptr;
+  std::atomic<size_t> next{0};
+  std::vector<std::thread> th;
+  void work() {
+    for (size_t i; (i = next.fetch_add(1, std::memory_order_relaxed)) < pages.size();) {
+      StagePage &p = pages[i];
+      uint32_t got = 0;
+      while (got < p.len) {
+        const ssize_t r = ::pread(p.fd, dst + p.off + got, p.len - got, off_t(p.start + got));
+        if (r < 0 && errno == EINTR) continue;
+        if (r <= 0) {
+          p.err = r < 0 ? errno : -1;
+          break;
+        }
+        got += uint32_t(r);
       }
-      pages.push_back(pg);
     }
-    pages.back().nhit++;
-    std::memcpy(&hid[k * 16], ids[lk.id_idx[h]], 16);
-    slot[k] = h;
   }
+  void start(uint64_t bytes) {  // a thread per MiB to read, kFindReaders at the most
+    const size_t nt = std::min<size_t>({kFindReaders, pages.size(), size_t(bytes >> 20) + 1});
+    for (size_t t = 0; t < nt; t++) th.emplace_back([this] { work(); });
+  }
+  void wait() {
+    for (auto &t : th) t.join();
+    th.clear();
+  }
+  ~RoundRead() { wait(); }
+};
+
+static uint64_t find_stage_cap() {
+  if (const uint64_t v = g_find_stage_bytes.load(std::memory_order_relaxed)) return v;
+  static const uint64_t env = [] {
+    const char *e = std::getenv("TSG_FIND_STAGE_BYTES");
+    return e ? uint64_t(std::strtoull(e, nullptr, 10)) : 0;
+  }();
+  return env ? env : kFindStageDefault;
+}
+
+// One round on the device: steps (2) to (5) over `pages`, whose hit ranges index `hid` (16 bytes
+// per hit) and `res`. stage: the round's staged bytes (pinned), copied to dc.fstage first (the
+// pages' src already point there). The objects found are appended to `bytes` in hit order; doff
+// is where each lies in `bytes`. Returns the device time (ns). dc.mu is held.
+static uint64_t find_round(DeviceCtx &dc, std::vector<FindPage> &pages, const std::vector<uint8_t> &hid,
+                           const uint8_t *stage, uint64_t stage_bytes, const CrcArgs &crc, std::vector<FindHitOut> &res,
+                           std::vector<uint64_t> &doff, std::vector<uint8_t> &bytes) {
   const uint32_t np = uint32_t(pages.size());
-  std::lock_guard<std::mutex> lkd(dc.mu);
-  resident_quit(dc);  // (the resident search launch holds every CU's LDS)
-  HIP_OK(hipSetDevice(dc.ordinal));
+  const size_t nh = hid.size() / 16;
+  res.assign(nh, FindHitOut{0, 0, TSG_E_NOT_FOUND});
+  doff.assign(nh, 0);
+  if (np == 0) return 0;
   hipStream_t s = dc.stream;
   HIP_OK(hipEventRecord(dc.ev0, s));
+  if (stage_bytes) HIP_OK(hipMemcpyAsync(dc.fstage.p, stage, stage_bytes, hipMemcpyHostToDevice, s));
   // (2) sizes
   DevBuf &dpages = dc.fpages, &dhid = dc.fhits, &dres = dc.fres, &darena = dc.farena;
   dpages.ensure(size_t(np) * sizeof(FindPage));
@@ -618,8 +641,6 @@ void device_find(DeviceCtx &dc, const std::vector<std::pair<uint32_t, V2Block *>
   darena.ensure(std::max<uint64_t>(total, 16));
   HIP_OK(hipMemcpyAsync(dpages.p, pages.data(), size_t(np) * sizeof(FindPage), hipMemcpyHostToDevice, s));
   // (3) decode
-  CrcArgs crc;
-  crc_tables(crc);
   dc.fcrc.ensure(sizeof(CrcArgs));
   HIP_OK(hipMemcpyAsync(dc.fcrc.p, &crc, sizeof(CrcArgs), hipMemcpyHostToDevice, s));
   find_decode_kernel<<<np, kFindThreads, 0, s>>>(static_cast<FindPage *>(dpages.p), static_cast<uint8_t *>(darena.p),
@@ -649,17 +670,16 @@ void device_find(DeviceCtx &dc, const std::vector<std::pair<uint32_t, V2Block *>
                                                static_cast<const uint8_t *>(darena.p),
                                                static_cast<const uint8_t *>(dhid.p), static_cast<FindHitOut *>(dres.p));
   HIP_OK(hipGetLastError());
-  std::vector<FindHitOut> res(nh);
   HIP_OK(hipMemcpyAsync(res.data(), dres.p, nh * sizeof(FindHitOut), hipMemcpyDeviceToHost, s));
   HIP_OK(hipStreamSynchronize(s));
   // (5) gather the found objects
-  std::vector<uint64_t> doff(nh, 0);
   uint64_t obytes = 0;
   for (size_t k = 0; k < nh; k++) {
     doff[k] = obytes;
     if (res[k].status == TSG_OK) obytes += res[k].len;
   }
-  out.bytes.resize(obytes);
+  const uint64_t base = bytes.size();
+  bytes.resize(base + obytes);
   if (obytes) {
     dc.fdst.ensure(obytes);
     dc.foff.ensure(nh * 8);
@@ -669,13 +689,175 @@ void device_find(DeviceCtx &dc, const std::vector<std::pair<uint32_t, V2Block *>
                                                     static_cast<const uint8_t *>(darena.p),
                                                     static_cast<uint8_t *>(dc.fdst.p));
     HIP_OK(hipGetLastError());
-    HIP_OK(hipMemcpyAsync(out.bytes.data(), dc.fdst.p, obytes, hipMemcpyDeviceToHost, s));
+    HIP_OK(hipMemcpyAsync(bytes.data() + base, dc.fdst.p, obytes, hipMemcpyDeviceToHost, s));
   }
   HIP_OK(hipEventRecord(dc.ev1, s));
   HIP_OK(hipStreamSynchronize(s));
+  for (auto &o : doff) o += base;
   float ms = 0;
   HIP_OK(hipEventElapsedTime(&ms, dc.ev0, dc.ev1));
-  out.kernel_ns += uint64_t(double(ms) * 1e6);
+  return uint64_t(double(ms) * 1e6);
+}
+
+void device_find(DeviceCtx &dc, const std::vector<std::pair<uint32_t, V2Block *>> &blocks, const uint8_t (*ids)[16],
+                 size_t nids, const tsg_lookup_opts *opts, FindOut &out) {
+  LookupOut lk;
+  device_lookup(dc, blocks, ids, nids, opts, lk);
+  out = FindOut();
+  const size_t nh = lk.id_idx.size();
+  out.id_idx.assign(lk.id_idx.begin(), lk.id_idx.end());
+  out.block_idx.assign(lk.block_idx.begin(), lk.block_idx.end());
+  out.status.assign(nh, TSG_E_NOT_FOUND);
+  out.obj_off.assign(nh, 0);
+  out.obj_len.assign(nh, 0);
+  out.kernel_ns = lk.kernel_ns;
+  if (nh == 0) return;
+  std::unordered_map<uint32_t, const V2Block *> by_idx;
+  for (auto &bp : blocks) by_idx[bp.first] = bp.second;
+  // (1) distinct pages, hits grouped by page
+  std::vector<uint32_t> order(nh);
+  std::iota(order.begin(), order.end(), 0u);
+  std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) {
+    return lk.block_idx[a] != lk.block_idx[b] ? lk.block_idx[a] < lk.block_idx[b] : lk.rec[a] < lk.rec[b];
+  });
+  std::vector<FindPage> pages;
+  std::vector<uint8_t> hid(nh * 16, 0);  // ids in page order
+  std::vector<uint32_t> slot(nh);        // page order -> hit
+  std::vector<StagePage> od;             // the pages to read from their files, in page order
+  std::vector<uint32_t> od_len;
+  for (size_t k = 0; k < nh; k++) {
+    const uint32_t h = order[k];
+    const V2Block *b = by_idx.at(lk.block_idx[h]);
+    if (pages.empty() || k == 0 || lk.block_idx[order[k - 1]] != lk.block_idx[h] || lk.rec[order[k - 1]] != lk.rec[h]) {
+      FindPage pg{};
+      pg.hit0 = uint32_t(k);
+      if (!b->d_data && b->data_fd < 0) {
+        pg.status = TSG_E_UNSUPPORTED;  // data file neither resident nor held open
+      } else if (lk.start[h] + lk.len[h] > b->data_len) {
+        pg.status = TSG_E_CORRUPT;  // ReadAt past the end of the data file
+      } else {
+        pg.len = lk.len[h];
+        pg.enc = uint32_t(b->enc);
+        pg.status = TSG_OK;
+        if (b->d_data) {
+          pg.src = b->d_data + lk.start[h];
+        } else {  // (src: once its round's staging offset is known)
+          od.push_back(StagePage{b->data_fd, lk.start[h], 0, lk.len[h], uint32_t(pages.size()), 0});
+          od_len.push_back(lk.len[h]);
+        }
+      }
+      pages.push_back(pg);
+    }
+    pages.back().nhit++;
+    std::memcpy(&hid[k * 16], ids[lk.id_idx[h]], 16);
+    slot[k] = h;
+  }
+  FindRoundPlan plan;
+  plan_find_rounds(od_len.data(), od_len.size(), find_stage_cap(), plan);
+  for (size_t i = 0; i < od.size(); i++) od[i].off = plan.offsets[i];
+  const size_t nr = plan.rounds.size();
+  uint64_t stage_max = 0;
+  for (auto &r : plan.rounds) stage_max = std::max(stage_max, r.bytes);
+  static const CrcArgs crc = [] {
+    CrcArgs c;
+    crc_tables(c);
+    return c;
+  }();
+  // The pinned buffers and their readers. They have a lock of their own, taken before dc.mu:
+  // round 0 is read from the files before the device is taken from its other callers and the
+  // resident search launch is told to leave, so a cold file holds up other finds over on-demand
+  // blocks of this device only. (Later rounds are read while the call's own kernels run.)
+  std::unique_lock<std::mutex> stage_lk(dc.fstage_mu, std::defer_lock);
+  RoundRead rd[2];
+  auto start_read = [&](size_t r) {
+    RoundRead &R = rd[r & 1];
+    const FindRound &fr = plan.rounds[r];
+    R.pages.assign(od.begin() + fr.first, od.begin() + fr.first + fr.count);
+    R.dst = static_cast<uint8_t *>(dc.fstage_host[r & 1].p);
+    R.next.store(0);
+    R.start(fr.bytes);
+  };
+  if (!od.empty()) {
+    stage_lk.lock();
+    HIP_OK(hipSetDevice(dc.ordinal));
+    // sized once for the call's largest round (+ 64: a decoder's wide load past a page's last
+    // byte stays inside)
+    for (size_t i = 0; i < std::min<size_t>(nr, 2); i++) dc.fstage_host[i].ensure(stage_max + 64);
+    start_read(0);
+    rd[0].wait();
+  }
+  std::lock_guard<std::mutex> lkd(dc.mu);
+  resident_quit(dc);  // (the resident search launch holds every CU's LDS)
+  HIP_OK(hipSetDevice(dc.ordinal));
+  std::vector<FindHitOut> res(nh);  // per hit in page order
+  std::vector<uint64_t> doff(nh, 0);
+  if (od.empty()) {  // every page resident: one round over the batch as it stands
+    out.kernel_ns += find_round(dc, pages, hid, nullptr, 0, crc, res, doff, out.bytes);
+    dc.find_rounds++;
+  } else {
+    dc.fstage.ensure(stage_max + 64);
+    std::vector<uint8_t> is_od(pages.size(), 0);
+    for (auto &p : od) is_od[p.page] = 1;
+    // round r: its on-demand pages, and in round 0 every other page too, in page order. Every
+    // round's objects are gathered straight behind the earlier rounds' in out.bytes.
+    std::vector<uint32_t> hits;  // the rounds' hits one after the other: page-order hit of each
+    std::vector<FindHitOut> rres;
+    std::vector<uint64_t> rdoff;
+    std::vector<std::pair<FindHitOut, uint64_t>> got(nh);  // per page-order hit: its result, where its object lies
+    for (size_t r = 0; r < nr; r++) {
+      const FindRound &fr = plan.rounds[r];
+      std::vector<uint32_t> take;  // page indexes
+      if (r == 0) {
+        const uint32_t end = fr.first + fr.count < od.size() ? od[fr.first + fr.count].page : uint32_t(pages.size());
+        for (uint32_t p = 0; p < pages.size(); p++)
+          if (!is_od[p] || p < end) take.push_back(p);
+      } else {
+        for (uint32_t i = fr.first; i < fr.first + fr.count; i++) take.push_back(od[i].page);
+      }
+      RoundRead &R = rd[r & 1];
+      R.wait();
+      if (r + 1 < nr) start_read(r + 1);  // (its buffer: round r - 1's copy has completed)
+      for (const StagePage &p : R.pages) {
+        FindPage &pg = pages[p.page];
+        pg.src = static_cast<const uint8_t *>(dc.fstage.p) + p.off;
+        if (!p.err) dc.find_read_bytes += p.len;
+        if (p.err) {
+          pg.status = TSG_E_CORRUPT;
+          out.read_error = "data file: page at " + std::to_string(p.start) + " (" + std::to_string(p.len) +
+                           " bytes): " + (p.err > 0 ? std::strerror(p.err) : "the file ends inside the page");
+        }
+      }
+      std::vector<FindPage> rp;
+      std::vector<uint8_t> rhid;
+      const size_t h0 = hits.size();
+      for (uint32_t p : take) {
+        FindPage pg = pages[p];
+        for (uint32_t j = 0; j < pg.nhit; j++) hits.push_back(pg.hit0 + j);
+        rhid.insert(rhid.end(), hid.begin() + size_t(pg.hit0) * 16, hid.begin() + size_t(pg.hit0 + pg.nhit) * 16);
+        pg.hit0 = uint32_t(hits.size() - h0) - pg.nhit;
+        rp.push_back(pg);
+      }
+      out.kernel_ns += find_round(dc, rp, rhid, R.dst, fr.bytes, crc, rres, rdoff, out.bytes);
+      dc.find_rounds++;
+      for (size_t j = 0; j < rres.size(); j++) got[hits[h0 + j]] = {rres[j], rdoff[j]};
+    }
+    // Page order, as one round would have left the objects. The rounds' hits follow each other in
+    // page order already unless resident pages, which ride in round 0, lie behind staged pages of
+    // a later round: only then the objects are moved.
+    bool sorted = true;
+    for (size_t k = 0; k < nh && sorted; k++) sorted = hits[k] == k;
+    std::vector<uint8_t> moved;
+    if (!sorted) moved.resize(out.bytes.size());
+    uint64_t obytes = 0;
+    for (size_t k = 0; k < nh; k++) {
+      res[k] = got[k].first;
+      doff[k] = sorted ? got[k].second : obytes;
+      if (res[k].status != TSG_OK) continue;
+      if (!sorted && res[k].len) std::memcpy(&moved[obytes], &out.bytes[got[k].second], res[k].len);
+      obytes += res[k].len;
+    }
+    if (!sorted) out.bytes.swap(moved);
+  }
   for (size_t k = 0; k < nh; k++) {
     const uint32_t h = slot[k];
     out.status[h] = res[k].status;

@@ -21,7 +21,12 @@
 // 200 blocks x 1 M probes: ~0.45 GB of slab reads instead of ~19 GB of bloom reads.
 #include <hip/hip_runtime.h>
 
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
 #include <algorithm>
+#include <cerrno>
 #include <cstring>
 
 #include "devctx.hpp"
@@ -747,6 +752,19 @@ void v2block_open(Ctx &c, V2Block &b, const std::string &dir, int device_hint) {
   if (!rdir.empty()) b.d_dir = static_cast<uint32_t *>(up(rdir.data(), rdir.size() * 4));
   // the data file for findOne on the device (pages stay compressed in HBM)
   b.enc = enc.empty() ? -1 : parse_encoding(enc);
+  if (b.data_mode == TSG_V2_DATA_ON_DEMAND) {
+    // the file stays on disk, held open: device_find reads the hit pages of each call (find.hip)
+    const std::string path = dir + "/data";
+    b.data_fd = ::open(path.c_str(), O_RDONLY | O_CLOEXEC);
+    if (b.data_fd < 0) {
+      if (errno != ENOENT) fail(TSG_E_IO, "open " + path + ": " + std::strerror(errno));
+      return;  // (no data file: its hits report TSG_E_UNSUPPORTED, as those of a resident open)
+    }
+    struct stat st;
+    if (fstat(b.data_fd, &st) != 0) fail(TSG_E_IO, "fstat " + path + ": " + std::strerror(errno));
+    b.data_len = uint64_t(st.st_size);
+    return;
+  }
   std::vector<uint8_t> data;
   if (!std::getenv("TSG_V2_NO_DATA") && read_file(dir + "/data", data)) {
     b.d_data = static_cast<const uint8_t *>(up(data.data(), data.size()));
@@ -755,6 +773,8 @@ void v2block_open(Ctx &c, V2Block &b, const std::string &dir, int device_hint) {
 }
 
 void v2block_free(V2Block &b) {
+  if (b.data_fd >= 0) ::close(b.data_fd);
+  b.data_fd = -1;
   if (!b.dc) return;
   std::lock_guard<std::mutex> lk(b.dc->mu);
   (void)hipSetDevice(b.dc->ordinal);

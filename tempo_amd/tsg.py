@@ -44,6 +44,9 @@ ENC_SNAPPY = 6
 ENC_ZSTD = 7
 ENC_NAMES = ["none", "gzip", "lz4-64k", "lz4-256k", "lz4-1M", "lz4", "snappy", "zstd", "s2"]  # backend.Encoding.String
 
+V2_DATA_RESIDENT = 0   # tsg_v2block_open_mode: the data file copied to the device at the open
+V2_DATA_ON_DEMAND = 1  # ... kept on disk; tsg_find_ids reads the hit pages per call
+
 SEARCH_TIME_SCAN = 1  # tsg_search_opts.flags: HIP events around the scan kernel
 SEARCH_TIME_ALL = 2   # ... and around the whole device sequence
 SEARCH_TIME_DEFER = 4  # events around the search kernel, read later by Engine.kernel_times()
@@ -170,7 +173,7 @@ EXPORTED = [
     "tsg_pipeline_new", "tsg_pipeline_query", "tsg_pipeline_free", "tsg_pipeline_matches_header",
     "tsg_block_open", "tsg_block_open_pages", "tsg_block_open_mem", "tsg_block_clone", "tsg_wal_block_open", "tsg_wal_block_open_mem", "tsg_wal_block_refresh", "tsg_wal_block_refresh_mem", "tsg_block_close", "tsg_block_info_get", "tsg_block_tags",
     "tsg_block_tag_values", "tsg_free", "tsg_search", "tsg_result_free", "tsg_kernel_times", "tsg_results_combine",
-    "tsg_v2block_open", "tsg_v2block_close", "tsg_lookup_ids", "tsg_lookup_result_free", "tsg_find_ids",
+    "tsg_v2block_open", "tsg_v2block_open_mode", "tsg_v2block_close", "tsg_lookup_ids", "tsg_lookup_result_free", "tsg_find_ids",
     "tsg_find_result_free", "tsg_proto_block_open", "tsg_proto_block_close", "tsg_proto_block_info",
     "tsg_proto_search", "tsg_proto_search_batch", "tsg_proto_result_free", "tsg_go_parse", "tsg_write_v2_block", "tsg_write_v2_block_pages",
     "tsg_write_search_block", "tsg_write_wal_search", "tsg_fb_search_entry", "tsg_fb_search_header", "tsg_synth_search_block",
@@ -240,6 +243,7 @@ def lib():
         L.tsg_kernel_times.argtypes = [vp, C.POINTER(C.c_uint64), C.c_size_t, C.POINTER(C.c_size_t)]
         L.tsg_results_combine.argtypes = [C.POINTER(_Result), C.c_uint32, C.POINTER(C.POINTER(_Result))]
         L.tsg_v2block_open.argtypes = [vp, C.c_char_p, C.c_int, C.POINTER(vp)]
+        L.tsg_v2block_open_mode.argtypes = [vp, C.c_char_p, C.c_int, C.c_uint32, C.POINTER(vp)]
         L.tsg_v2block_close.argtypes = [vp]
         L.tsg_lookup_ids.argtypes = [vp, C.POINTER(vp), C.c_size_t, vp, C.c_size_t, C.POINTER(_LookupOpts),
                                      C.POINTER(C.POINTER(_LookupResult))]
@@ -732,9 +736,10 @@ class Engine:
         (a launch that left on its idle timeout as a query was posted), quits, slot reads the
         kernel rejected (check mismatch), narrow queries launched plainly because another process
         has a context on the GPU, narrow queries launched plainly (any reason), XCD-split samples, narrow
-        queries served by a terms-first kernel instance (resident or plain launches)."""
+        queries served by a terms-first kernel instance (resident or plain launches); then find()'s bytes
+        read from the data files of V2_DATA_ON_DEMAND blocks and the find rounds run."""
         keys = ("launches", "queries", "relaunches", "quits", "rejects", "cotenant_queries", "plain_queries",
-                "xsplit_samples", "terms_first_queries")
+                "xsplit_samples", "terms_first_queries", "find_read_bytes", "find_rounds")
         buf = (C.c_uint64 * len(keys))()
         _check(lib().tsg_device_counters(self.h, dev, buf, len(keys)))
         return dict(zip(keys, list(buf)))
@@ -765,8 +770,10 @@ class Engine:
         finally:
             lib().tsg_result_free(rp)
 
-    def open_v2block(self, path: str, device: int = 0) -> "V2Block":
-        return V2Block(self, path, device)
+    def open_v2block(self, path: str, device: int = 0, data_mode: int = V2_DATA_RESIDENT) -> "V2Block":
+        """tsg_v2block_open_mode. V2_DATA_ON_DEMAND: the data file stays on disk, held open, and find()
+        reads the pages its hits name, per call (include/tsg.h)."""
+        return V2Block(self, path, device, data_mode)
 
     def lookup(self, blocks: Sequence["V2Block"], ids, time_start=0, time_end=0, block_start=None,
                block_end=None):
@@ -932,7 +939,8 @@ def debug_set(name: str, value: int) -> None:
     """tsg_debug_set: process-wide test hooks ("res_torn": the next `value` resident posts are
     written torn, then repaired; DESIGN.md §4. "zstd_writer_flags": forced forms of the zstd page writer; "zstd_find_lane": 1 selects the
     one-lane zstd page decoder of find; "lz4_writer_flags": checksum bits of the lz4 page
-    writer, include/tsg.h)."""
+    writer; "find_stage_bytes": find()'s staging cap over V2_DATA_ON_DEMAND blocks, 0 = the default,
+    include/tsg.h)."""
     _check(lib().tsg_debug_set(name.encode(), value))
 
 
@@ -1088,9 +1096,9 @@ class ProtoBlock:
 
 
 class V2Block:
-    def __init__(self, eng: Engine, path: str, device: int = 0):
+    def __init__(self, eng: Engine, path: str, device: int = 0, data_mode: int = V2_DATA_RESIDENT):
         self.h = C.c_void_p()
-        _check(lib().tsg_v2block_open(eng.h, path.encode(), device, C.byref(self.h)))
+        _check(lib().tsg_v2block_open_mode(eng.h, path.encode(), device, data_mode, C.byref(self.h)))
         eng._open.add(self)
 
     def close(self):
